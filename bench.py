@@ -3,7 +3,13 @@ Msamples/sec (whole node) on the 1080p modern-kitchen-class scene, sample-split
 across N GPUs of one node with RCCL all-reduce (scripts/ddp_render.py parity).
 
 Driver contract:
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run builds the scene, warms up, times the K steps and prints the
+result line; it measures nothing else.  --dump-outputs DIR additionally
+saves the accumulation buffers as they stand after the last timed step
+(scene, seeds and sampler streams are fixed, so two builds can be compared
+array for array).  --full is where secondary measurements go; there are
+none today, so it changes nothing yet.
 N>1 is launched via torch.distributed.run (one rank per GPU over RCCL);
 each rank renders `--spp-per-step` samples per pixel per step (weak scaling);
 the radiance accumulators are spp-weighted all-reduced like the reference's
@@ -14,6 +20,32 @@ import json
 import os
 import sys
 import time
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(outdir, buffers):
+    """Write what the timed path left behind — the renderer's radiance
+    accumulator (H, W, 4: RGB sums + sample count) and luminance-moment
+    buffer (H, W, 2) after the last timed step — as float32 .npy files.
+    Frames whose buffers exceed the byte budget are written as the same
+    fixed, seeded subset of pixels (rows of the (H*W, C) view, ascending)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {}
+    for name, buf in buffers.items():
+        a = buf.cpu().numpy() if hasattr(buf, "cpu") else np.asarray(buf)
+        arrays[name] = np.ascontiguousarray(a, dtype=np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        n_pix = next(iter(arrays.values())).shape[0] * next(iter(arrays.values())).shape[1]
+        bytes_per_pix = total // n_pix
+        keep = np.sort(np.random.default_rng(0).choice(
+            n_pix, size=DUMP_BUDGET_BYTES // bytes_per_pix, replace=False))
+        arrays = {k: a.reshape(n_pix, -1)[keep] for k, a in arrays.items()}
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def main():
@@ -31,7 +63,16 @@ def main():
                     help="all-reduce the accumulator every this many steps")
     ap.add_argument("--cpu", action="store_true", help="CPU reference path (debug)")
     ap.add_argument("--sbvh", action="store_true", help="spatial-split BVH for the scene")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write the accumulation buffers "
+                         "the last step left (accum, var) to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (none exist yet: "
+                         "a plain run times the headline figure and nothing else; "
+                         "anything added beyond it belongs behind this flag)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     import torch
 
@@ -122,6 +163,9 @@ def main():
         te = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed = float(te.item())
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"accum": rend.accum, "var": rend.var})
 
     n_gpus = world_size if distributed else (0 if args.cpu else 1)
     samples = float(args.width) * args.height * args.spp_per_step * args.steps * max(world_size, 1)

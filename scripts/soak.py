@@ -8,6 +8,7 @@ Usage: python scripts/soak.py [--minutes 5] [--cpu] [--width 960] [--height 540]
 import argparse
 import os
 import sys
+import tempfile
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -37,6 +38,7 @@ def main():
     t_end = time.time() + args.minutes * 60.0
     it = 0
     spp = 1 if args.cpu else 8
+    ckdir = tempfile.TemporaryDirectory(prefix="hippt_soak_")
     while time.time() < t_end:
         for name, r in rs:
             r.render(spp)
@@ -53,7 +55,7 @@ def main():
         rk.renderer.reset()
         # checkpoint round trip on the volumetric renderer
         _, rv = rs[2]
-        ck = "/tmp/soak_ck.npz"
+        ck = os.path.join(ckdir.name, "soak_ck.npz")
         rv.save_state(ck, step=it)
         extra = rv.load_state(ck)
         assert int(extra["step"]) == it
@@ -62,6 +64,7 @@ def main():
             print(f"[soak] iter {it}, {max(0.0, t_end - time.time()):.0f}s left, "
                   f"frames: " + " ".join(f"{n}={r.avg_frame_time():.0f}ms"
                                          for n, r in rs), flush=True)
+    ckdir.cleanup()
     print(f"[soak] OK: {it} iterations, all renderers finite")
 
 

@@ -77,6 +77,55 @@ def test_bench_contract_cpu():
     assert line["scaling"] == "weak"
 
 
+def test_bench_dump_outputs_cpu(tmp_path):
+    """--dump-outputs writes the accumulation buffers of the last timed step
+    as float32 .npy; same arguments -> same arrays; --steps/--warmup really
+    set the step counts (alpha channel = accumulated spp); --full keeps the
+    result line intact."""
+    outs = []
+    for i, extra in enumerate(([], ["--full"])):
+        d = tmp_path / f"dump{i}"
+        res = subprocess.run([sys.executable, "bench.py", "--cpu", "--width", "96",
+                              "--height", "54", "--spp-per-step", "2", "--steps", "3",
+                              "--warmup", "1", "--dump-outputs", str(d)] + extra,
+                             cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr
+        line = json.loads(res.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["warmup"] == 1
+        assert line["ms_per_step"] > 0 and line["dtype"] == "fp32"
+        assert sorted(os.listdir(d)) == ["accum.npy", "var.npy"]
+        outs.append({n: np.load(d / f"{n}.npy") for n in ("accum", "var")})
+    a = outs[0]
+    assert a["accum"].shape == (54, 96, 4) and a["accum"].dtype == np.float32
+    assert a["var"].shape == (54, 96, 2) and a["var"].dtype == np.float32
+    np.testing.assert_array_equal(a["accum"][..., 3], (3 + 1) * 2)
+    assert np.isfinite(a["accum"]).all() and a["accum"][..., :3].mean() > 0
+    for n in a:
+        np.testing.assert_array_equal(a[n], outs[1][n])
+
+
+def test_bench_dump_outputs_budget(tmp_path, monkeypatch):
+    """Buffers over the byte budget are written as one fixed, seeded subset
+    of pixels shared by every array, and stay within the budget."""
+    monkeypatch.syspath_prepend(ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 24 * 100)
+    rng = np.random.default_rng(1)
+    accum = rng.random((20, 30, 4), dtype=np.float32)
+    var = rng.random((20, 30, 2), dtype=np.float32)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), {"accum": accum, "var": var})
+    a, v = np.load(tmp_path / "a" / "accum.npy"), np.load(tmp_path / "a" / "var.npy")
+    assert a.shape == (100, 4) and v.shape == (100, 2)
+    assert a.nbytes + v.nbytes <= 24 * 100
+    np.testing.assert_array_equal(a, np.load(tmp_path / "b" / "accum.npy"))
+    # both arrays hold the same pixels, each one a row of the source frame
+    flat_a, flat_v = accum.reshape(-1, 4), var.reshape(-1, 2)
+    idx = [int(np.flatnonzero((flat_a == row).all(axis=1))[0]) for row in a]
+    assert idx == sorted(set(idx))
+    np.testing.assert_array_equal(v, flat_v[idx])
+
+
 def test_tile_split_two_ranks(tmp_path):
     """Tile mode: 2 ranks x row bands at full spp == single-process full
     render at the same spp (same per-pixel sampler streams; SUM-merge of
