@@ -42,6 +42,33 @@ using uarr = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>;
 
 Vec3 to_vec3(const std::vector<float>& v) { return {v[0], v[1], v[2]}; }
 
+// HIPPT_SUPER_N = voxels per majorant supercell per axis (A/B: finer cells
+// skip empty space tighter but cost more DDA steps); shared by the dense and
+// the brick supergrid builders so both cut the grid into the same cells
+int super_cell_voxels() {
+    static const int SUP = [] {
+        const char* e = getenv("HIPPT_SUPER_N");
+        int v = e ? atoi(e) : 16;  // smoke 1080p: sup4 74.4, sup8 84.9, sup16 89.6 Msps
+        return v < 2 ? 2 : (v > 64 ? 64 : v);
+    }();
+    return SUP;
+}
+
+// Fold one voxel into the supergrid: max into every supercell within +-1
+// voxel (the stochastic-offset lookup samples up to +-0.5 voxel outside).
+inline void super_splat(std::vector<float>& sup, const MediumParams& m, int SUP,
+                        int ix, int iy, int iz, float v) {
+    int cx0 = std::max(0, (ix - 1) / SUP), cx1 = std::min(m.sx - 1, (ix + 1) / SUP);
+    int cy0 = std::max(0, (iy - 1) / SUP), cy1 = std::min(m.sy - 1, (iy + 1) / SUP);
+    int cz0 = std::max(0, (iz - 1) / SUP), cz1 = std::min(m.sz - 1, (iz + 1) / SUP);
+    for (int cz = cz0; cz <= cz1; ++cz)
+        for (int cy = cy0; cy <= cy1; ++cy)
+            for (int cx = cx0; cx <= cx1; ++cx) {
+                float& s = sup[(size_t(cz) * m.sy + cy) * m.sx + cx];
+                s = fmaxf(s, v);
+            }
+}
+
 // Max level count of a 4-wide tree (host walk; used to gate halved-stack
 // traversal kernels like the wavefront dual walk).
 int bvh4_tree_depth(const BVH4Node* nodes, int n) {
@@ -71,6 +98,8 @@ struct SceneHolder {
     std::vector<MediumParams> media;          // host pointers inside
     std::vector<farr> media_density, media_temp;
     std::vector<std::vector<float>> media_super;   // majorant supergrids (raw max)
+    std::vector<std::vector<int32_t>> media_bricks;  // brick tables (brick layout)
+    std::vector<int> media_nbricks;           // per medium: pool bricks, -1 = not bricked
     std::vector<farr> tex_data;
     std::vector<TexView> tex_host;
     std::vector<int> emitter_prims;
@@ -271,13 +300,7 @@ struct SceneHolder {
             // 1-voxel dilation (the stochastic-offset lookup samples up to
             // +-0.5 voxel outside the cell); scale is applied in the walk so
             // update_medium's scale changes need no rebuild
-            // HIPPT_SUPER_N = voxels per supercell per axis (A/B: finer
-            // cells skip empty space tighter but cost more DDA steps)
-            static const int SUP = [] {
-                const char* e = getenv("HIPPT_SUPER_N");
-                int v = e ? atoi(e) : 16;  // smoke 1080p: sup4 74.4, sup8 84.9, sup16 89.6 Msps
-                return v < 2 ? 2 : (v > 64 ? 64 : v);
-            }();
+            const int SUP = super_cell_voxels();
             if (getenv("HIPPT_NO_SUPER")) {
                 // A/B hook: single global majorant (round-1 behavior)
                 m.sx = m.sy = m.sz = 0;
@@ -294,15 +317,7 @@ struct SceneHolder {
                     for (int ix = 0; ix < m.nx; ++ix) {
                         float v = dd[(size_t(iz) * m.ny + iy) * m.nx + ix];
                         if (v <= 0.f) continue;
-                        int cx0 = std::max(0, (ix - 1) / SUP), cx1 = std::min(m.sx - 1, (ix + 1) / SUP);
-                        int cy0 = std::max(0, (iy - 1) / SUP), cy1 = std::min(m.sy - 1, (iy + 1) / SUP);
-                        int cz0 = std::max(0, (iz - 1) / SUP), cz1 = std::min(m.sz - 1, (iz + 1) / SUP);
-                        for (int cz = cz0; cz <= cz1; ++cz)
-                            for (int cy = cy0; cy <= cy1; ++cy)
-                                for (int cx = cx0; cx <= cx1; ++cx) {
-                                    float& s = sup[(size_t(cz) * m.sy + cy) * m.sx + cx];
-                                    s = fmaxf(s, v);
-                                }
+                        super_splat(sup, m, SUP, ix, iy, iz, v);
                     }
             media_super.push_back(std::move(sup));
             m.super = media_super.back().data();
@@ -319,7 +334,162 @@ struct SceneHolder {
             }
         }
         media.push_back(m);
+        media_nbricks.push_back(-1);
         return (int)media.size() - 1;
+    }
+
+    // Grid medium in the brick layout (hippt/scene/sparse_grid.py): `coords`
+    // (n,3) sorted (bz,by,bx) brick coordinates, `density` / `temperature`
+    // (n,512) brick pools in the same order.  Majorant, mean and supergrid
+    // are what add_medium computes for the equivalent dense grid, visiting
+    // only resident bricks (everything else is background 0).
+    int add_medium_sparse(std::vector<float> sigma_a, std::vector<float> sigma_s,
+                          int phase_id, std::vector<float> grid_lo, std::vector<float> grid_hi,
+                          std::vector<int> shape, iarr coords, farr density,
+                          py::object temperature,
+                          float scale, float emission_scale, float temp_scale) {
+        MediumParams m{};
+        m.sigma_a = Vec4(sigma_a[0], sigma_a[1], sigma_a[2], 0.f);
+        m.sigma_s = Vec4(sigma_s[0], sigma_s[1], sigma_s[2], 0.f);
+        m.type = MED_GRID; m.phase_id = phase_id;
+        m.scale = scale; m.emission_scale = emission_scale; m.temp_scale = temp_scale;
+        if (shape.size() != 3 || shape[0] <= 0 || shape[1] <= 0 || shape[2] <= 0)
+            throw std::runtime_error("sparse grid shape must be three positive dims (nz,ny,nx)");
+        m.nz = shape[0]; m.ny = shape[1]; m.nx = shape[2];
+        m.bnx = (m.nx + 7) / 8; m.bny = (m.ny + 7) / 8; m.bnz = (m.nz + 7) / 8;
+        if (coords.ndim() != 2 || coords.shape(1) != 3)
+            throw std::runtime_error("brick coords must be (n,3)");
+        const size_t nb = (size_t)coords.shape(0);
+        if ((size_t)density.size() != nb * 512)
+            throw std::runtime_error("density bricks must hold 512 floats per brick coord");
+        farr temp;
+        if (!temperature.is_none()) {
+            temp = temperature.cast<farr>();
+            if ((size_t)temp.size() != nb * 512)
+                throw std::runtime_error("temperature bricks must hold 512 floats per brick coord");
+        }
+        const size_t cells = (size_t)m.bnx * m.bny * m.bnz;
+        if (cells > (size_t)INT32_MAX) throw std::runtime_error("brick table too large");
+        std::vector<int32_t> table(cells, -1);
+        const int32_t* cc = coords.data();
+        for (size_t b = 0; b < nb; ++b) {
+            int bz = cc[3 * b], by = cc[3 * b + 1], bx = cc[3 * b + 2];
+            if (bz < 0 || bz >= m.bnz || by < 0 || by >= m.bny || bx < 0 || bx >= m.bnx)
+                throw std::runtime_error("brick coord outside the brick table");
+            int32_t& cell = table[(size_t(bz) * m.bny + by) * m.bnx + bx];
+            if (cell >= 0) throw std::runtime_error("duplicate brick coord");
+            cell = (int32_t)b;
+        }
+        const float* pool = density.data();
+        // max is order-free; the mean's double sum walks voxels in the dense
+        // (z,y,x) order over resident bricks only — skipped voxels are exact
+        // zeros, so it reproduces the dense sum bit for bit
+        float mx = 0.f; double sum = 0.0;
+        for (size_t i = 0; i < nb * 512; ++i) mx = fmaxf(mx, pool[i]);
+        std::vector<int32_t> row;
+        for (int bz = 0; bz < m.bnz; ++bz)
+            for (int z = 0; z < 8 && bz * 8 + z < m.nz; ++z)
+                for (int by = 0; by < m.bny; ++by) {
+                    row.clear();
+                    const int32_t* trow = &table[(size_t(bz) * m.bny + by) * m.bnx];
+                    for (int bx = 0; bx < m.bnx; ++bx)
+                        if (trow[bx] >= 0) row.push_back(trow[bx]);
+                    if (row.empty()) continue;
+                    for (int y = 0; y < 8 && by * 8 + y < m.ny; ++y)
+                        for (int32_t b : row) {
+                            const float* v = pool + size_t(b) * 512 + (z << 6 | y << 3);
+                            for (int x = 0; x < 8; ++x) sum += v[x];
+                        }
+                }
+        const size_t n = (size_t)m.nx * m.ny * m.nz;
+        m.majorant = mx * scale;
+        m.avg_density = (float)(sum / std::max<size_t>(n, 1)) * scale;
+        if (!getenv("HIPPT_NO_SUPER")) {
+            const int SUP = super_cell_voxels();
+            m.sx = (m.nx + SUP - 1) / SUP;
+            m.sy = (m.ny + SUP - 1) / SUP;
+            m.sz = (m.nz + SUP - 1) / SUP;
+            std::vector<float> sup((size_t)m.sx * m.sy * m.sz, 0.f);
+            for (size_t b = 0; b < nb; ++b) {
+                int z0 = cc[3 * b] * 8, y0 = cc[3 * b + 1] * 8, x0 = cc[3 * b + 2] * 8;
+                const float* v = pool + b * 512;
+                for (int z = 0; z < 8 && z0 + z < m.nz; ++z)
+                    for (int y = 0; y < 8 && y0 + y < m.ny; ++y)
+                        for (int x = 0; x < 8 && x0 + x < m.nx; ++x) {
+                            float d = v[z << 6 | y << 3 | x];
+                            if (d <= 0.f) continue;
+                            super_splat(sup, m, SUP, x0 + x, y0 + y, z0 + z, d);
+                        }
+            }
+            media_super.push_back(std::move(sup));
+            m.super = media_super.back().data();
+        }
+        Vec3 lo = to_vec3(grid_lo), hi = to_vec3(grid_hi);
+        m.grid_lo = Vec4(lo, 0.f);
+        Vec3 ext = hi - lo;
+        m.grid_inv_extent = Vec4(1.f / ext.x, 1.f / ext.y, 1.f / ext.z, 0.f);
+        media_bricks.push_back(std::move(table));
+        m.bricks = media_bricks.back().data();
+        // an empty grid keeps null pools: every table cell is -1, so the
+        // lookup never touches them and nothing of size zero is uploaded
+        if (nb > 0) {
+            media_density.push_back(density);
+            m.density = media_density.back().data();
+            if (!temperature.is_none()) {
+                media_temp.push_back(temp);
+                m.temperature = media_temp.back().data();
+            }
+        }
+        media.push_back(m);
+        media_nbricks.push_back((int)nb);
+        return (int)media.size() - 1;
+    }
+
+    // Majorant supergrid of medium i as a (sz,sy,sx) array (empty when the
+    // medium has none) plus (majorant, avg_density); layout-equivalence tests.
+    py::tuple medium_super(int i) {
+        if (i < 0 || i >= (int)media.size()) throw std::runtime_error("bad medium index");
+        const MediumParams& m = media[i];
+        farr out({(py::ssize_t)(m.super ? m.sz : 0), (py::ssize_t)m.sy, (py::ssize_t)m.sx});
+        if (m.super) std::memcpy(out.mutable_data(), m.super, sizeof(float) * out.size());
+        return py::make_tuple(out, m.majorant, m.avg_density);
+    }
+
+    // Per-medium storage report (Scene.info()["media"]).
+    py::list media_info() {
+        py::list out;
+        for (size_t i = 0; i < media.size(); ++i) {
+            const MediumParams& m = media[i];
+            py::dict d;
+            size_t vox = (size_t)m.nx * m.ny * m.nz;
+            size_t pools = (m.density ? 1 : 0) + (m.temperature ? 1 : 0);
+            size_t bytes = 4 * (size_t)m.sx * m.sy * m.sz * (m.super ? 1 : 0);
+            if (m.type != MED_GRID) {
+                d["layout"] = "homogeneous";
+                d["shape"] = py::none();
+                d["n_bricks"] = 0;
+                d["occupancy"] = 0.0;
+            } else if (m.bricks) {
+                size_t cells = (size_t)m.bnx * m.bny * m.bnz;
+                size_t nb = (size_t)media_nbricks[i];
+                d["layout"] = "bricks";
+                d["shape"] = py::make_tuple(m.nz, m.ny, m.nx);
+                d["n_bricks"] = nb;
+                d["occupancy"] = (double)nb / (double)cells;
+                bytes += 4 * cells + 2048 * nb * pools;
+            } else {
+                d["layout"] = "dense";
+                d["shape"] = py::make_tuple(m.nz, m.ny, m.nx);
+                d["n_bricks"] = 0;
+                d["occupancy"] = 1.0;
+                bytes += 4 * vox * pools;
+            }
+            d["bytes_host"] = bytes;
+            d["bytes_device"] = has_dev ? bytes : (size_t)0;
+            d["bytes_dense_equiv"] = 4 * vox;
+            out.append(d);
+        }
+        return out;
     }
 
     void update_medium(int i, std::vector<float> sigma_a, std::vector<float> sigma_s,
@@ -390,6 +560,8 @@ struct SceneHolder {
         sv.env_w = env_w;
         sv.env_h = env_h;
         sv.cam_medium = cam_medium;
+        sv.media_bricks = 0;
+        for (const MediumParams& m : media) if (m.bricks) sv.media_bricks = 1;
         sv.cam = cam;
         sv.md = md;
         sv.bvh4_depth = bvh4_depth;
@@ -464,14 +636,18 @@ struct SceneHolder {
         // media: re-point grids at device copies
         media_dev = media;
         for (size_t i = 0; i < media.size(); ++i) {
-            if (media[i].density) {
-                size_t n = (size_t)media[i].nx * media[i].ny * media[i].nz;
-                media_dev[i].density = upload_vec(media[i].density, n);
+            // pool size: resident bricks (brick layout) or the whole grid
+            size_t n_vox = media[i].bricks
+                ? (size_t)media_nbricks[i] * 512
+                : (size_t)media[i].nx * media[i].ny * media[i].nz;
+            if (media[i].bricks) {
+                size_t cells = (size_t)media[i].bnx * media[i].bny * media[i].bnz;
+                media_dev[i].bricks = upload_vec(media[i].bricks, cells);
             }
-            if (media[i].temperature) {
-                size_t n = (size_t)media[i].nx * media[i].ny * media[i].nz;
-                media_dev[i].temperature = upload_vec(media[i].temperature, n);
-            }
+            if (media[i].density)
+                media_dev[i].density = upload_vec(media[i].density, n_vox);
+            if (media[i].temperature)
+                media_dev[i].temperature = upload_vec(media[i].temperature, n_vox);
             if (media[i].super) {
                 size_t n = (size_t)media[i].sx * media[i].sy * media[i].sz;
                 media_dev[i].super = upload_vec(media[i].super, n);
@@ -793,6 +969,9 @@ PYBIND11_MODULE(_C, m) {
         .def("set_emitter_sel", &SceneHolder::set_emitter_sel)
         .def("add_phase", &SceneHolder::add_phase)
         .def("add_medium", &SceneHolder::add_medium)
+        .def("add_medium_sparse", &SceneHolder::add_medium_sparse)
+        .def("media_info", &SceneHolder::media_info)
+        .def("medium_super", &SceneHolder::medium_super)
         .def("update_medium", &SceneHolder::update_medium)
         .def("add_texture", &SceneHolder::add_texture)
         .def("set_camera", &SceneHolder::set_camera)

@@ -38,6 +38,7 @@ HD void cross_boundary(VolStack& st, const ObjInfo& obj, const Vec3& d, const Ve
 // Transmittance estimate along a shadow path (re-trace across null interfaces
 // accumulating per-segment medium transmittance; reference
 // occlusion_transmittance_estimate, megakernel_vpt.cu:104-201).
+template <bool BRICKS = true>
 HD Vec3 transmittance_estimate(const SceneView& sv, Vec3 from, const Vec3& wi, float dist,
                                TravCtx tc,
                                VolStack stack, Sampler& sp) {
@@ -51,7 +52,7 @@ HD Vec3 transmittance_estimate(const SceneView& sv, Vec3 from, const Vec3& wi, f
         float seg = hit.prim_idx >= 0 ? hit.t : remaining;
         int med = stack.current();
         if (med >= 0) {
-            tr *= medium_transmittance(sv.media[med], r, seg, sp);
+            tr *= medium_transmittance<BRICKS>(sv.media[med], r, seg, sp);
             if (tr.max_elem() < 1e-6f) return Vec3(0.f);
         }
         if (hit.prim_idx < 0) break;  // reached the light
@@ -67,6 +68,8 @@ HD Vec3 transmittance_estimate(const SceneView& sv, Vec3 from, const Vec3& wi, f
     return tr;
 }
 
+// BRICKS: the scene may hold brick-layout grid media (medium.h grid_voxel)
+template <bool BRICKS = true>
 HD Vec3 trace_path_volumetric(const SceneView& sv, Ray ray, Sampler& sp, TravCtx tc = {}) {
     float path_lambda = 0.f;
     Vec3 L(0.f), thp(1.f);
@@ -88,7 +91,7 @@ HD Vec3 trace_path_volumetric(const SceneView& sv, Ray ray, Sampler& sp, TravCtx
         bool scattered = false;
         float t_event = t_surf;
         if (med >= 0) {
-            MediumSample ms = medium_sample(sv.media[med], ray, t_surf, sp);
+            MediumSample ms = medium_sample<BRICKS>(sv.media[med], ray, t_surf, sp);
             thp *= ms.local_thp;
             if (thp.is_zero() || thp.has_nan()) break;
             if (ms.scattered) { scattered = true; t_event = ms.dist; }
@@ -101,7 +104,7 @@ HD Vec3 trace_path_volumetric(const SceneView& sv, Ray ray, Sampler& sp, TravCtx
             const MediumParams& mp = sv.media[med];
             const PhaseParams& ph = sv.phases[mp.phase_id];
             // medium emission (blackbody, query_emission parity)
-            Vec3 em = medium_emission(mp, pos, sp);
+            Vec3 em = medium_emission<BRICKS>(mp, pos, sp);
             if (!em.is_zero() && tof_in_range(sv.md, path_time)) L += thp * em;
             // NEE from the volume point
             if (sv.n_emitters > 0) {
@@ -114,7 +117,7 @@ HD Vec3 trace_path_volumetric(const SceneView& sv, Ray ray, Sampler& sp, TravCtx
                     float dist = to_l.length();
                     Vec3 wi = to_l * (1.f / fmaxf(dist, 1e-9f));
                     float fp = phase_eval(ph, ray.d.dot(wi));
-                    Vec3 tr = transmittance_estimate(sv, pos, wi, dist - EPSILON, tc, stack, sp);
+                    Vec3 tr = transmittance_estimate<BRICKS>(sv, pos, wi, dist - EPSILON, tc, stack, sp);
                     if (!tr.is_zero()) {
                         float light_pdf = er.pdf * epdf;
                         float w = er.delta ? 1.f : mis_weight(light_pdf, fp);
@@ -180,7 +183,7 @@ HD Vec3 trace_path_volumetric(const SceneView& sv, Ray ray, Sampler& sp, TravCtx
                     Vec3 f = bsdf_eval(bsdf, -ray.d, wi, it, sv.textures);
                     if (!f.is_zero()) {
                         float sh_max = (sv.emitters[ei].type == EM_ENVMAP ? ENVMAP_DIST : dist) - 2.f * EPSILON;
-                        Vec3 tr = transmittance_estimate(sv, pos, wi, sh_max, tc, stack, sp);
+                        Vec3 tr = transmittance_estimate<BRICKS>(sv, pos, wi, sh_max, tc, stack, sp);
                         if (!tr.is_zero()) {
                             float light_pdf = er.pdf * epdf;
                             float w = er.delta ? 1.f

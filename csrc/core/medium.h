@@ -10,11 +10,16 @@
 // nearest-neighbor lookup, blackbody emission :97-102).
 //
 // MI355X-native change: instead of walking NanoVDB trees on-device (long
-// scalar-dependent pointer chases) we use a dense float grid in a flat
-// device buffer plus a majorant SUPERGRID that delta/ratio tracking DDA
-// over; the host layer loads grids from .npy / .nvdb files
-// (hippt/scene/nvdb.py converts NanoVDB trees to dense on the host) or
-// procedural generators.
+// scalar-dependent pointer chases) the voxels live in a flat device buffer
+// plus a majorant SUPERGRID that delta/ratio tracking DDA over.  Two voxel
+// layouts share every line of the tracking code:
+//   dense  — one (nz,ny,nx) float array (default; every shipped grid),
+//   bricks — a brick table over ceil(n/8) cells per axis holding a pool
+//            index or -1, plus a pool of resident 8^3 bricks (512 floats
+//            each): two dependent loads per lookup, no dense expansion of
+//            large mostly-empty volumes (hippt/scene/sparse_grid.py).
+// The host layer loads grids from .npy / .nvdb files (hippt/scene/nvdb.py)
+// or procedural generators.
 #pragma once
 #include "phase.h"
 #include "spectrum.h"
@@ -31,16 +36,21 @@ struct alignas(16) MediumParams {
     Vec4 sigma_s;          // scattering
     Vec4 grid_lo;          // world-space grid bounds
     Vec4 grid_inv_extent;  // 1 / (hi - lo)
-    const float* density;      // nx*ny*nz density voxels (nullptr for homogeneous)
-    const float* temperature;  // optional emission temperature grid
+    const float* density;      // nx*ny*nz density voxels (nullptr for homogeneous);
+                               // brick pool (512 floats/brick) when `bricks` is set
+    const float* temperature;  // optional emission temperature grid (same layout)
     // majorant supergrid: per-supercell RAW density max (HIPPT_SUPER_N
     // voxels/cell per axis, default 16; dilated by 1 voxel for the
     // stochastic-offset lookup); the tracking
     // walks DDA over it so null collisions never happen in empty space
     // (reference uses one global majorant from tree extrema, vol_grid.cu:131)
     const float* super;
+    // brick layout: bnx*bny*bnz table of pool indices (-1 = empty brick,
+    // background 0); nullptr = dense layout
+    const int32_t* bricks;
     int32_t sx, sy, sz;
     int32_t nx, ny, nz;
+    int32_t bnx, bny, bnz;
     int32_t type;
     int32_t phase_id;
     float majorant;        // max sigma_t over the grid (delta tracking)
@@ -48,8 +58,8 @@ struct alignas(16) MediumParams {
     float scale;           // density multiplier
     float emission_scale;  // blackbody emission brightness
     float temp_scale;      // temperature units -> Kelvin
-    float pad0;
 };
+static_assert(sizeof(MediumParams) % 16 == 0, "MediumParams must stay 16-byte granular");
 
 struct MediumSample {
     Vec3 local_thp;   // throughput multiplier up to the event
@@ -58,6 +68,30 @@ struct MediumSample {
 };
 
 // ---------------------------------------------------------------- density
+// Raw voxel fetch for either layout.  Both branches only LOAD; the caller
+// applies any arithmetic after the merge, so the two layouts feed identical
+// values into identical instructions (bit-equal renders).
+//
+// BRICKS (here and on every function down from trace_path_volumetric) says
+// whether the scene may hold brick media at all.  The vpt kernel is built
+// once per value: a scene without brick media runs the BRICKS=false
+// instantiation, whose tracking loops carry no layout test, no extra live
+// registers and no brick code (the shared kernel cost the dense smoke bench
+// 3-5%, profiles/README.md); BRICKS=true tests m.bricks per lookup and
+// serves both layouts.
+template <bool BRICKS = true>
+HD float grid_voxel(const MediumParams& m, const float* pool, int ix, int iy, int iz) {
+    if constexpr (BRICKS) {
+        if (m.bricks) {
+            int b = m.bricks[(size_t(iz >> 3) * m.bny + (iy >> 3)) * m.bnx + (ix >> 3)];
+            return b < 0 ? 0.f
+                         : pool[size_t(b) * 512 + (((iz & 7) << 6) | ((iy & 7) << 3) | (ix & 7))];
+        }
+    }
+    return pool[(size_t(iz) * m.ny + iy) * m.nx + ix];
+}
+
+template <bool BRICKS = true>
 HD float grid_density_at(const MediumParams& m, const Vec3& p, Sampler* jitter) {
     Vec3 g = (p - m.grid_lo.xyz()) * m.grid_inv_extent.xyz();
     if (g.x < 0.f || g.y < 0.f || g.z < 0.f || g.x >= 1.f || g.y >= 1.f || g.z >= 1.f) return 0.f;
@@ -72,9 +106,10 @@ HD float grid_density_at(const MediumParams& m, const Vec3& p, Sampler* jitter) 
     int ix = clampv((int)fx, 0, m.nx - 1);
     int iy = clampv((int)fy, 0, m.ny - 1);
     int iz = clampv((int)fz, 0, m.nz - 1);
-    return m.density[(size_t(iz) * m.ny + iy) * m.nx + ix] * m.scale;
+    return grid_voxel<BRICKS>(m, m.density, ix, iy, iz) * m.scale;
 }
 
+template <bool BRICKS = true>
 HD float grid_temperature_at(const MediumParams& m, const Vec3& p) {
     if (!m.temperature) return 0.f;
     Vec3 g = (p - m.grid_lo.xyz()) * m.grid_inv_extent.xyz();
@@ -82,7 +117,7 @@ HD float grid_temperature_at(const MediumParams& m, const Vec3& p) {
     int ix = clampv((int)(g.x * m.nx), 0, m.nx - 1);
     int iy = clampv((int)(g.y * m.ny), 0, m.ny - 1);
     int iz = clampv((int)(g.z * m.nz), 0, m.nz - 1);
-    return m.temperature[(size_t(iz) * m.ny + iy) * m.nx + ix];
+    return grid_voxel<BRICKS>(m, m.temperature, ix, iy, iz);
 }
 
 // ------------------------------------------------------- homogeneous medium
@@ -201,6 +236,7 @@ struct SuperDDA {
 // ------------------------------------------------------------- grid medium
 // Delta-tracking distance sampling (reference vol_grid.cu:128-150), DDA'd
 // over the majorant supergrid when present.
+template <bool BRICKS = true>
 HD MediumSample grid_sample(const MediumParams& m, const Ray& ray, float t_max, Sampler& sp) {
     MediumSample r{};
     r.local_thp = Vec3(1.f);
@@ -223,7 +259,7 @@ HD MediumSample grid_sample(const MediumParams& m, const Ray& ray, float t_max, 
             for (; it < 16384; ++it) {
                 t -= logf(fmaxf(1.f - sp.next1f(), 1e-12f)) * inv_c;
                 if (t >= s1) break;
-                float dens = grid_density_at(m, ray.at(t), &sp);
+                float dens = grid_density_at<BRICKS>(m, ray.at(t), &sp);
                 if (sp.next1f() < dens * inv_c) {
                     if (sp.next1f() < a_mean) {
                         r.local_thp = alb * (1.f / a_mean);
@@ -243,7 +279,7 @@ HD MediumSample grid_sample(const MediumParams& m, const Ray& ray, float t_max, 
     for (int it = 0; it < 4096; ++it) {
         t -= logf(fmaxf(1.f - sp.next1f(), 1e-12f)) * inv_maj;
         if (t >= t_max) break;
-        float dens = grid_density_at(m, ray.at(t), &sp);
+        float dens = grid_density_at<BRICKS>(m, ray.at(t), &sp);
         float sig_t = dens;  // density IS sigma_t (scale folded in)
         if (sp.next1f() < sig_t * inv_maj) {
             // real collision: scatter with albedo, absorb otherwise
@@ -265,6 +301,7 @@ HD MediumSample grid_sample(const MediumParams& m, const Ray& ray, float t_max, 
 // Ratio-tracking transmittance with Russian roulette below Tr=0.1
 // (reference vol_grid.cu:177-198); residual-ratio around avg_density when
 // the control is useful (vol_grid.cu:153-175).
+template <bool BRICKS = true>
 HD Vec3 grid_transmittance(const MediumParams& m, const Ray& ray, float dist, Sampler& sp) {
     float maj = m.majorant;
     if (maj <= 0.f) return Vec3(1.f);
@@ -280,7 +317,7 @@ HD Vec3 grid_transmittance(const MediumParams& m, const Ray& ray, float dist, Sa
             for (; it < 16384; ++it) {
                 t -= logf(fmaxf(1.f - sp.next1f(), 1e-12f)) * inv_c;
                 if (t >= s1) break;
-                float dens = grid_density_at(m, ray.at(t), &sp);
+                float dens = grid_density_at<BRICKS>(m, ray.at(t), &sp);
                 tr *= fmaxf(0.f, 1.f - dens * inv_c);
                 if (tr < 0.1f) {  // Russian roulette termination
                     if (sp.next1f() >= tr * 10.f) return Vec3(0.f);
@@ -297,7 +334,7 @@ HD Vec3 grid_transmittance(const MediumParams& m, const Ray& ray, float dist, Sa
     for (int it = 0; it < 4096; ++it) {
         t -= logf(fmaxf(1.f - sp.next1f(), 1e-12f)) * inv_maj;
         if (t >= dist) break;
-        float dens = grid_density_at(m, ray.at(t), &sp);
+        float dens = grid_density_at<BRICKS>(m, ray.at(t), &sp);
         tr *= fmaxf(0.f, 1.f - dens * inv_maj);
         if (tr < 0.1f) {  // Russian roulette termination
             if (sp.next1f() >= tr * 10.f) return Vec3(0.f);
@@ -309,20 +346,23 @@ HD Vec3 grid_transmittance(const MediumParams& m, const Ray& ray, float dist, Sa
 }
 
 // ------------------------------------------------------------ dispatch API
+template <bool BRICKS = true>
 HD MediumSample medium_sample(const MediumParams& m, const Ray& ray, float t_max, Sampler& sp) {
     if (m.type == MED_HOMOGENEOUS) return homogeneous_sample(m, t_max, sp);
-    return grid_sample(m, ray, t_max, sp);
+    return grid_sample<BRICKS>(m, ray, t_max, sp);
 }
 
+template <bool BRICKS = true>
 HD Vec3 medium_transmittance(const MediumParams& m, const Ray& ray, float dist, Sampler& sp) {
     if (m.type == MED_HOMOGENEOUS) return homogeneous_transmittance(m, dist);
-    return grid_transmittance(m, ray, dist, sp);
+    return grid_transmittance<BRICKS>(m, ray, dist, sp);
 }
 
 // Blackbody emission at a point (temperature grid -> RGB, vol_grid.cu:97-102).
+template <bool BRICKS = true>
 HD Vec3 medium_emission(const MediumParams& m, const Vec3& p, Sampler& sp) {
     if (m.type != MED_GRID || !m.temperature || m.emission_scale <= 0.f) return Vec3(0.f);
-    float T = grid_temperature_at(m, p) * m.temp_scale;
+    float T = grid_temperature_at<BRICKS>(m, p) * m.temp_scale;
     if (T < 100.f) return Vec3(0.f);
     return blackbody_rgb(T) * m.emission_scale;
 }

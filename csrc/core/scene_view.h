@@ -65,6 +65,9 @@ struct SceneView {
     const MediumParams* media; int n_media;
     const PhaseParams* phases;
     int cam_medium;    // medium the camera sits in (-1 = vacuum)
+    // some grid medium uses the brick layout: the vpt launcher picks the
+    // kernel instantiation that carries the brick lookup (medium.h)
+    int media_bricks;
     // camera + depth caps
     Camera cam;
     MaxDepthParams md;

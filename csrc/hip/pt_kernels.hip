@@ -34,7 +34,9 @@ __device__ inline int xcd_swizzle(int flat, int n_tiles) {
 // lds_n = traversal-stack entries per thread held in (dynamic) LDS, bvh4.h.
 // The LDS block allocation (lds_n x 8 B x 256 threads) is also the occupancy
 // governor: 12/16/20/26/40 entries -> 6/5/4/3/2 waves per SIMD.
-template <int RENDERER, int MINW = 6>
+// BRICKS (R_VOLUME_PT only): the scene holds brick-layout grid media; the
+// dense-only instantiation keeps the tracking loops free of the layout test.
+template <int RENDERER, int MINW = 6, bool BRICKS = false>
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(MINW, MINW)))   // exact residency: the LDS
 // stack caps blocks/CU at MINW waves/SIMD, so the allocator may spend the
@@ -104,7 +106,7 @@ void k_render(SceneView sv, float* __restrict__ accum, float* __restrict__ var,
         Sampler sp(uint32_t(pix), uint32_t(spp0 + s) * SEED_SCALER + seed);
         Ray ray = sv.cam.gen_ray(px, py, sp, spp0 + s);
         Vec3 L(0.f);
-        if constexpr (RENDERER == R_VOLUME_PT) L = clamp_radiance(sv, trace_path_volumetric(sv, ray, sp, tc));
+        if constexpr (RENDERER == R_VOLUME_PT) L = clamp_radiance(sv, trace_path_volumetric<BRICKS>(sv, ray, sp, tc));
         else if constexpr (RENDERER == R_DEPTH) L = Vec3(trace_depth(sv, ray, tc));
         else if constexpr (RENDERER == R_BVH_COST) { Vec2 c = trace_bvh_cost(sv, ray); L = Vec3(c.x, c.y, 0.f); }
         else L = trace_path(sv, ray, sp, tc);
@@ -252,7 +254,12 @@ int launch_render(const SceneView& sv, float* accum, float* var,
         break;
     }
     case R_VOLUME_PT:
-        if (occ_v == 4)
+        if (sv.media_bricks) {
+            if (occ_v == 4)
+                hipLaunchKernelGGL((k_render<R_VOLUME_PT, 4, true>), grid, block, shmem, st, sv, accum, var, spp0, nspp, seed, swiz(), lds_n, n_cached, y0, y1, spp_map, aux);
+            else
+                hipLaunchKernelGGL((k_render<R_VOLUME_PT, 6, true>), grid, block, shmem, st, sv, accum, var, spp0, nspp, seed, swiz(), lds_n, n_cached, y0, y1, spp_map, aux);
+        } else if (occ_v == 4)
             hipLaunchKernelGGL((k_render<R_VOLUME_PT, 4>), grid, block, shmem, st, sv, accum, var, spp0, nspp, seed, swiz(), lds_n, n_cached, y0, y1, spp_map, aux);
         else
             hipLaunchKernelGGL((k_render<R_VOLUME_PT, 6>), grid, block, shmem, st, sv, accum, var, spp0, nspp, seed, swiz(), lds_n, n_cached, y0, y1, spp_map, aux);

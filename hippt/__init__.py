@@ -47,4 +47,5 @@ def has_gpu() -> bool:
 
 from .pyrender import PythonRenderer  # noqa: E402,F401
 from .scene.scene import Scene, SceneDesc  # noqa: E402,F401
+from .scene.sparse_grid import SparseGrid  # noqa: E402,F401
 from .render.renderer import Renderer  # noqa: E402,F401

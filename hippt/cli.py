@@ -18,7 +18,7 @@ import time
 def main(argv=None):
     ap = argparse.ArgumentParser("hippt.cli", description=__doc__)
     ap.add_argument("scene", help="scene XML path or procedural name "
-                                  "(cornell|kitchen|sports-car|smoke)")
+                                  "(cornell|kitchen|sports-car|smoke|sparse-smoke)")
     ap.add_argument("-o", "--output", default="render.png")
     ap.add_argument("--spp", type=int, default=None, help="override sample count")
     ap.add_argument("--renderer", default=None,
@@ -46,7 +46,8 @@ def main(argv=None):
     else:
         from .scene import procedural
         gens = {"cornell": procedural.cornell_box, "kitchen": procedural.kitchen,
-                "sports-car": procedural.sports_car, "smoke": procedural.smoke_box}
+                "sports-car": procedural.sports_car, "smoke": procedural.smoke_box,
+                "sparse-smoke": procedural.sparse_smoke_box}
         if args.scene not in gens:
             ap.error(f"unknown scene {args.scene}")
         desc = gens[args.scene]()
@@ -73,6 +74,16 @@ def main(argv=None):
     print(f"[hippt] prims={info['n_prims']} nodes={info['n_nodes']} "
           f"bsdfs={info['n_bsdfs']} emitters={info['n_emitters']} "
           f"sah={info.get('sah_cost', 0):.1f}")
+    for mi, med in enumerate(info.get("media", [])):
+        if med["layout"] == "homogeneous":
+            continue
+        nz, ny, nx = med["shape"]
+        mib = 1.0 / (1 << 20)
+        print(f"[hippt] medium {mi}: {med['layout']} {nx}x{ny}x{nz} "
+              f"bricks={med['n_bricks']} occupancy={100.0 * med['occupancy']:.2f}% "
+              f"host={med['bytes_host'] * mib:.1f} MiB "
+              f"device={med['bytes_device'] * mib:.1f} MiB "
+              f"dense-equiv={med['bytes_dense_equiv'] * mib:.1f} MiB")
     chunk = 16 if device >= 0 else 4
     done = 0
     while done < spp:

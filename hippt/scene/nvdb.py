@@ -1,12 +1,14 @@
-"""Minimal NanoVDB (.nvdb) file I/O: read float grids into dense arrays,
-write dense arrays as valid .nvdb files.
+"""Minimal NanoVDB (.nvdb) file I/O: read float grids into dense arrays or
+SparseGrid bricks, write either as valid .nvdb files.
 
 Capability parity: the reference's GridVolumeManager reads .nvdb files and
-uploads NanoVDB trees to the GPU (/root/reference/src/impl/vol_grid.cu:
-216-342, nanovdb::io::readGrids + deviceUpload).  The MI355X build renders
-volumes from DENSE density grids (csrc/core/medium.h delta/ratio tracking
-over a (nz,ny,nx) float array + majorant supergrid), so .nvdb ingestion is
-a host-side conversion: sparse tree -> dense array + world-space bounds.
+uploads NanoVDB trees to the GPU (reference src/impl/vol_grid.cu:216-342,
+nanovdb::io::readGrids + deviceUpload).  The MI355X build renders volumes
+from flat voxel buffers (csrc/core/medium.h delta/ratio tracking + majorant
+supergrid), so .nvdb ingestion is a host-side conversion: sparse tree ->
+dense (nz,ny,nx) array, or -> SparseGrid bricks (read_nvdb(sparse=True):
+8^3 leaves scatter straight into 8^3 bricks, the index bounding box is
+never expanded) + world-space bounds.
 
 Scope (documented subset, checked loudly):
   * NanoVDB ABI 32.x float grids (LevelSet/FogVolume/Unknown classes),
@@ -31,6 +33,8 @@ from __future__ import annotations
 import struct
 
 import numpy as np
+
+from .sparse_grid import SparseGrid
 
 MAGIC = 0x304244566F6E614E          # "NanoVDB0" little-endian
 ALIGN = 32
@@ -75,24 +79,13 @@ class NvdbError(ValueError):
 
 
 # --------------------------------------------------------------------- write
-def write_nvdb(path, density, voxel_size=1.0, origin=(0, 0, 0),
-               grid_name="density", grid_class=GC_FOG,
-               world_origin=(0.0, 0.0, 0.0), codec="none"):
-    """Write a dense (nz, ny, nx) float32 array as a single-grid .nvdb file
-    (codec NONE).  `origin` is the index-space coordinate of voxel [0,0,0];
-    world transform is a uniform scale by `voxel_size` plus a translation by
-    `world_origin`.  Zero voxels become inactive background (the file stores
-    only non-empty 8^3 leaves)."""
+def _bricks_of_dense(density):
+    """Leaf collection for a dense array -> (shape, [((bz,by,bx), vals zyx)],
+    vmin, vmax, active voxel count); bricks in (bz, by, bx) order."""
     d = np.ascontiguousarray(np.asarray(density, np.float32))
     if d.ndim != 3:
         raise NvdbError("density must be (nz, ny, nx)")
     nz, ny, nx = d.shape
-    oi, oj, ok = (int(v) for v in origin)
-    if min(oi, oj, ok) < 0 or max(oi + nx, oj + ny, ok + nz) > 4096:
-        raise NvdbError("writer supports index bounds within one upper node "
-                        "(origin >= 0, extent <= 4096)")
-
-    # ---- collect non-empty leaves (index space: i=x, j=y, k=z)
     # pad the array to 8-multiples for easy slicing
     px, py, pz = (-nx) % 8, (-ny) % 8, (-nz) % 8
     dp = np.pad(d, ((0, pz), (0, py), (0, px)))
@@ -100,9 +93,55 @@ def write_nvdb(path, density, voxel_size=1.0, origin=(0, 0, 0),
     blocks = dp.reshape(lz, 8, ly, 8, lx, 8).transpose(0, 2, 4, 1, 3, 5)
     nonzero = blocks.reshape(lz, ly, lx, -1).any(axis=-1)
     leaf_idx = np.argwhere(nonzero)          # (n, 3) in (bz, by, bx)
+    bricks = [((bz, by, bx), blocks[bz, by, bx]) for bz, by, bx in leaf_idx]
+    vmax = float(d.max()) if d.size else 0.0
+    vmin = float(d.min()) if d.size else 0.0
+    return d.shape, bricks, vmin, vmax, int(np.count_nonzero(d))
+
+
+def _bricks_of_sparse(g):
+    """Leaf collection for a SparseGrid: the same tuple _bricks_of_dense
+    gives for g.to_dense(), computed from the bricks alone."""
+    nz, ny, nx = g.shape
+    bricks = [(tuple(int(c) for c in g.coords[i]), g.values[i])
+              for i in range(g.n_bricks) if g.values[i].any()]
+    bd = g.brick_dims
+    if g.n_bricks == 0:
+        vmin = vmax = 0.0
+    elif g.n_bricks == bd[0] * bd[1] * bd[2]:
+        # fully resident: the zero padding of edge bricks is not grid data,
+        # and this dense form is no larger than the bricks themselves
+        d = g.to_dense()
+        vmin, vmax = float(d.min()), float(d.max())
+    else:
+        # some brick is absent, so background 0 is one of the grid's values
+        vmin = min(float(g.values.min()), 0.0)
+        vmax = max(float(g.values.max()), 0.0)
+    return g.shape, bricks, vmin, vmax, int(np.count_nonzero(g.values))
+
+
+def write_nvdb(path, density, voxel_size=1.0, origin=(0, 0, 0),
+               grid_name="density", grid_class=GC_FOG,
+               world_origin=(0.0, 0.0, 0.0), codec="none"):
+    """Write a dense (nz, ny, nx) float32 array, or a SparseGrid, as a
+    single-grid .nvdb file.  `origin` is the index-space coordinate of voxel
+    [0,0,0]; world transform is a uniform scale by `voxel_size` plus a
+    translation by `world_origin`.  Zero voxels become inactive background
+    (the file stores only non-empty 8^3 leaves); a SparseGrid's bricks are
+    written as leaves directly, without a dense intermediate."""
+    oi, oj, ok = (int(v) for v in origin)
+    if isinstance(density, SparseGrid):
+        shape, bricks, vmin, vmax, n_active = _bricks_of_sparse(density)
+    else:
+        shape, bricks, vmin, vmax, n_active = _bricks_of_dense(density)
+    nz, ny, nx = shape
+    if min(oi, oj, ok) < 0 or max(oi + nx, oj + ny, ok + nz) > 4096:
+        raise NvdbError("writer supports index bounds within one upper node "
+                        "(origin >= 0, extent <= 4096)")
+
+    # ---- non-empty leaves (index space: i=x, j=y, k=z), one per brick
     leaves = []                              # (origin_ijk, values (8,8,8) zyx)
-    for bz, by, bx in leaf_idx:
-        vals = blocks[bz, by, bx]            # (z, y, x)
+    for (bz, by, bx), vals in bricks:
         leaves.append(((oi + 8 * int(bx), oj + 8 * int(by), ok + 8 * int(bz)), vals))
 
     # group leaves under lower (16^3 leaves = 128^3 voxels) and upper nodes
@@ -116,8 +155,6 @@ def write_nvdb(path, density, voxel_size=1.0, origin=(0, 0, 0),
         uppers.setdefault(ukey, []).append((lkey, lvs))
     uppers = dict(sorted(uppers.items()))
 
-    vmax = float(d.max()) if d.size else 0.0
-    vmin = float(d.min()) if d.size else 0.0
     n_leaf = len(leaves)
     n_lower = len(lowers)
     n_upper = len(uppers)
@@ -167,7 +204,7 @@ def write_nvdb(path, density, voxel_size=1.0, origin=(0, 0, 0),
                     root_off - GRID_DATA_SIZE)
     t += struct.pack("<3I", n_leaf, n_lower, n_upper)
     t += struct.pack("<3I", 0, 0, 0)     # active tile counts per level
-    t += struct.pack("<Q", int(np.count_nonzero(d)))
+    t += struct.pack("<Q", n_active)
     t += b"\0" * (TREE_DATA_SIZE - len(t))
     buf[GRID_DATA_SIZE:GRID_DATA_SIZE + TREE_DATA_SIZE] = t
 
@@ -263,7 +300,7 @@ def write_nvdb(path, density, voxel_size=1.0, origin=(0, 0, 0),
 
     # ---- file wrapper
     name_file = grid_name.encode() + b"\0"
-    meta = struct.pack("<4Q", grid_size, grid_size, 0, int(np.count_nonzero(d)))
+    meta = struct.pack("<4Q", grid_size, grid_size, 0, n_active)
     meta += struct.pack("<II", GT_FLOAT, grid_class)
     meta += struct.pack("<6d", *wb_min, *wb_max)
     meta += struct.pack("<6i", *ib_min, *ib_max)
@@ -289,8 +326,10 @@ def write_nvdb(path, density, voxel_size=1.0, origin=(0, 0, 0),
 
 
 # ---------------------------------------------------------------------- read
-def _read_grid(blob):
-    """Parse one uncompressed NanoVDB float-grid blob -> dict."""
+def _read_grid(blob, sparse=False):
+    """Parse one uncompressed NanoVDB float-grid blob -> dict.  sparse=True
+    scatters the leaves into SparseGrid bricks anchored at index_min (key
+    "sparse") and never allocates the index bounding box (no "dense" key)."""
     magic, _cksum, version = struct.unpack_from("<QQI", blob, 0)
     if magic != MAGIC:
         raise NvdbError(f"bad NanoVDB grid magic 0x{magic:x}")
@@ -321,8 +360,32 @@ def _read_grid(blob):
     imin = np.array(ib[:3], np.int64)
     imax = np.array(ib[3:], np.int64)
     shape = (imax - imin + 1)                      # (x, y, z) extents
-    dense = np.full((int(shape[2]), int(shape[1]), int(shape[0])),
-                    background, np.float32)        # (z, y, x)
+    zs, ys, xs = int(shape[2]), int(shape[1]), int(shape[0])
+    if sparse:
+        if background != 0.0:
+            raise NvdbError(f"sparse read needs background 0, grid '{name}' has "
+                            f"background {background!r}; read it dense instead")
+        bricks = {}                                # (bz,by,bx) -> (8,8,8) zyx
+    else:
+        dense = np.full((zs, ys, xs), background, np.float32)   # (z, y, x)
+
+    def leaf_into_bricks(v, x0, y0, z0, x1, y1, z1):
+        # a leaf whose origin is not 8-aligned to index_min straddles up to
+        # 2x2x2 bricks: copy the overlap with each
+        for bz in range(z0 >> 3, ((z1 - 1) >> 3) + 1):
+            za, zb = max(z0, bz * 8), min(z1, bz * 8 + 8)
+            for by in range(y0 >> 3, ((y1 - 1) >> 3) + 1):
+                ya, yb = max(y0, by * 8), min(y1, by * 8 + 8)
+                for bx in range(x0 >> 3, ((x1 - 1) >> 3) + 1):
+                    xa, xb = max(x0, bx * 8), min(x1, bx * 8 + 8)
+                    src = v[za - z0:zb - z0, ya - y0:yb - y0, xa - x0:xb - x0]
+                    if not src.any():
+                        continue
+                    b = bricks.get((bz, by, bx))
+                    if b is None:
+                        b = bricks[(bz, by, bx)] = np.zeros((8, 8, 8), np.float32)
+                    b[za - bz * 8:zb - bz * 8, ya - by * 8:yb - by * 8,
+                      xa - bx * 8:xb - bx * 8] = src
 
     def leaf_into(leaf_base):
         org = struct.unpack_from("<3i", blob, leaf_base)
@@ -331,13 +394,15 @@ def _read_grid(blob):
         mask = np.unpackbits(np.frombuffer(blob, np.uint8, 64, leaf_base + 16),
                              bitorder="little").reshape(8, 8, 8).transpose(2, 1, 0)
         x0, y0, z0 = (int(org[a] - imin[a]) for a in range(3))
-        zs, ys, xs = dense.shape
         # clip (leaves may straddle the index bbox on badly formed files)
         v = np.where(mask > 0, v, background)
         z1, y1, x1 = min(z0 + 8, zs), min(y0 + 8, ys), min(x0 + 8, xs)
         if z0 < 0 or y0 < 0 or x0 < 0 or z1 <= z0 or y1 <= y0 or x1 <= x0:
             return
-        dense[z0:z1, y0:y1, x0:x1] = v[:z1 - z0, :y1 - y0, :x1 - x0]
+        if sparse:
+            leaf_into_bricks(v, x0, y0, z0, x1, y1, z1)
+        else:
+            dense[z0:z1, y0:y1, x0:x1] = v[:z1 - z0, :y1 - y0, :x1 - x0]
 
     def walk_lower(base):
         cm = np.frombuffer(blob, np.uint64, 64, base + 24 + 8 + 512)
@@ -359,9 +424,11 @@ def _read_grid(blob):
         if child != 0:
             walk_upper(root + child)
 
+    grid = ({"sparse": SparseGrid.from_bricks((zs, ys, xs), bricks)} if sparse
+            else {"dense": dense})
     return {
         "name": name,
-        "dense": dense,
+        **grid,
         "index_min": tuple(int(v) for v in imin),
         "voxel_size": tuple(float(v) for v in vsz),
         "world_min": tuple(wb[:3]),
@@ -373,9 +440,31 @@ def _read_grid(blob):
     }
 
 
-def read_nvdb(path):
+def peek_nvdb(path):
+    """Per-grid file metadata without touching the grid blobs -> list of
+    dicts with `shape` (nz,ny,nx of the index bbox) and `dense_nbytes`."""
+    with open(path, "rb") as f:
+        data = f.read(16)
+        magic, _version_, grid_count, codec = struct.unpack_from("<QIHH", data, 0)
+        if magic != MAGIC:
+            raise NvdbError(f"{path}: not a NanoVDB file (magic 0x{magic:x})")
+        out = []
+        for _ in range(grid_count):
+            meta = f.read(176)
+            grid_size, file_size = struct.unpack_from("<2Q", meta, 0)
+            ib = struct.unpack_from("<6i", meta, 88)
+            name_size, = struct.unpack_from("<I", meta, 136)
+            nx, ny, nz = (ib[3 + a] - ib[a] + 1 for a in range(3))
+            out.append({"shape": (nz, ny, nx), "dense_nbytes": 4 * nx * ny * nz})
+            f.seek(name_size + (file_size if codec == CODEC_ZIP else grid_size), 1)
+    return out
+
+
+def read_nvdb(path, sparse=False):
     """Read all float grids of a .nvdb file -> list of dicts with keys
-    name, dense (nz,ny,nx float32), index_min, voxel_size, world_min/max."""
+    name, dense (nz,ny,nx float32), index_min, voxel_size, world_min/max.
+    With sparse=True each dict carries `sparse` (a SparseGrid over the index
+    bbox) instead of `dense`; a nonzero background raises NvdbError."""
     with open(path, "rb") as f:
         data = f.read()
     magic, version, grid_count, codec = struct.unpack_from("<QIHH", data, 0)
@@ -405,5 +494,5 @@ def read_nvdb(path):
         else:
             blob = data[off:off + grid_size]
             off += grid_size
-        grids.append(_read_grid(blob))
+        grids.append(_read_grid(blob, sparse))
     return grids

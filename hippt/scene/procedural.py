@@ -406,3 +406,87 @@ def smoke_box(width=1280, height=720, spp=32, n_grid=96, emission=False,
     d.config.max_depth = 32
     d.config.max_volume = 64
     return d
+
+
+def sparse_smoke_density(n=512, seed=3):
+    """Thin rising plume as a SparseGrid of shape (n, n, n), built one
+    8-voxel z-slab at a time over the plume's bounding columns only: no
+    n^3 array ever exists.  Values in [0, ~1]; a few percent of the bricks
+    are resident."""
+    from .sparse_grid import BRICK, SparseGrid
+    rng = np.random.default_rng(seed)
+    # analytic turbulence: a few sine-product octaves with random phases
+    # (point-evaluable, unlike smoke_density's lattice noise)
+    freq = [rng.uniform(3.0, 6.0, 3) * (2 ** o) for o in range(4)]
+    phase = [rng.uniform(0.0, 2.0 * math.pi, 3) for _ in range(4)]
+    r_base, r_grow = 0.06, 0.20          # plume radius 0.06 .. 0.26 of the half width
+    r_max = r_base + r_grow
+
+    def coord(i):                        # voxel centre -> [-1, 1]
+        return (i + 0.5) * (2.0 / n) - 1.0
+
+    nb = (n + BRICK - 1) // BRICK
+    # brick columns the widest plume section can reach (x and z alike)
+    b_lo = max(0, int(math.floor((1.0 - r_max) * 0.5 * n)) // BRICK)
+    b_hi = min(nb, int(math.ceil((1.0 + r_max) * 0.5 * n)) // BRICK + 1)
+    iy = np.arange(nb * BRICK)
+    ix = np.arange(b_lo * BRICK, b_hi * BRICK)
+    y = ((iy + 0.5) / n).astype(np.float32)[None, :, None]            # [0, 1]
+    x = coord(ix).astype(np.float32)[None, None, :]
+    inside = ((iy < n)[None, :, None] & (ix < n)[None, None, :])
+    radius = r_base + r_grow * y
+    coords, values = [], []
+    for bz in range(b_lo, b_hi):
+        iz = np.arange(bz * BRICK, bz * BRICK + BRICK)
+        z = coord(iz).astype(np.float32)[:, None, None]
+        r = np.sqrt(x * x + z * z)
+        env = np.clip(1.0 - r / radius, 0.0, 1.0) * np.clip(1.2 - y, 0.0, 1.0)
+        turb = np.zeros_like(env)
+        amp = 1.0
+        for f, p in zip(freq, phase):
+            turb += amp * (np.sin(f[0] * x + p[0]) * np.sin(f[1] * y + p[1])
+                           * np.sin(f[2] * z + p[2]))
+            amp *= 0.5
+        slab = np.clip(env * (0.55 + 0.45 * np.abs(turb)) - 0.05, 0.0, None)
+        slab = np.where(inside & (iz < n)[:, None, None], slab, 0.0).astype(np.float32)
+        blocks = slab.reshape(BRICK, nb, BRICK, b_hi - b_lo, BRICK).transpose(1, 3, 0, 2, 4)
+        keep = (blocks != 0).any(axis=(2, 3, 4))
+        for by, bxl in np.argwhere(keep):
+            coords.append((bz, int(by), b_lo + int(bxl)))
+            values.append(blocks[by, bxl])
+    if not coords:
+        return SparseGrid((n, n, n), np.zeros((0, 3), np.int32),
+                          np.zeros((0, BRICK, BRICK, BRICK), np.float32))
+    vals = np.stack(values)
+    vals /= max(float(vals.max()), 1e-20)
+    return SparseGrid((n, n, n), np.asarray(coords, np.int32), vals)
+
+
+def sparse_smoke_box(width=1280, height=720, spp=32, n_grid=512, emission=False,
+                     renderer="vpt") -> SceneDesc:
+    """The smoke box with a large, mostly-empty plume grid in the brick
+    layout (SparseGrid): production-size volume, no asset file, no dense
+    n_grid^3 array at any point."""
+    from .sparse_grid import SparseGrid
+    d = cornell_box(width=width, height=height, spp=spp, max_depth=10,
+                    renderer=renderer, light_scale=30.0)
+    d.camera.width, d.camera.height = width, height
+    dens = sparse_smoke_density(n=n_grid)
+    temp = None
+    escale = 0.0
+    if emission:
+        temp = SparseGrid(dens.shape, dens.coords, dens.values * np.float32(4500.0))
+        escale = 2.0
+    dens = SparseGrid(dens.shape, dens.coords, dens.values * np.float32(18.0))
+    d.media = [MediumDesc(type="grid", sigma_a=(0.4, 0.45, 0.5), sigma_s=(3.5, 3.5, 3.5),
+                          phase="hg", g1=0.3, density=dens,
+                          temperature=temp, emission_scale=escale, temp_scale=1.0,
+                          grid_lo=(-0.7, 0.05, 0.5), grid_hi=(0.7, 1.75, 1.9))]
+    nb = len(d.bsdfs)
+    d.bsdfs.append(BsdfDesc(type="forward"))
+    d.objects.append(ObjectDesc(tris=box_mesh((-0.7, 0.05, 0.5), (0.7, 1.75, 1.9)),
+                                bsdf=nb, medium_in=0, cullable=True))
+    d.config.renderer = renderer
+    d.config.max_depth = 32
+    d.config.max_volume = 64
+    return d

@@ -16,6 +16,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from .. import C
+from .sparse_grid import SparseGrid, union_coords
 
 # BSDF type ids (must match csrc/core/bsdf.h)
 BSDF_TYPES = {
@@ -102,8 +103,10 @@ class MediumDesc:
     g1: float = 0.0
     g2: float = 0.0
     wmix: float = 0.5
-    density: Optional[np.ndarray] = None       # (nz,ny,nx) float32
-    temperature: Optional[np.ndarray] = None
+    # (nz,ny,nx) float32 ndarray (dense layout) or SparseGrid; if either
+    # grid is a SparseGrid the medium uses the brick layout for both
+    density: Optional[object] = None
+    temperature: Optional[object] = None
     grid_lo: Tuple[float, ...] = (0, 0, 0)
     grid_hi: Tuple[float, ...] = (1, 1, 1)
     scale: float = 1.0
@@ -241,9 +244,17 @@ class Scene:
             self.native.add_bsdf(ty, kd, ks, kg, ior, e0, e1, _tex_slots(b))
 
         # ---- phases + media
+        # A/B hook: HIPPT_SPARSE_GRID=1 stores ndarray grids in the brick
+        # layout (read per Scene, so one process can build both)
+        force_bricks = os.environ.get("HIPPT_SPARSE_GRID", "0") not in ("", "0")
         for m in d.media:
             pid = self.native.add_phase(PHASE_TYPES[m.phase], m.g1, m.g2, m.wmix)
             mty = 0 if m.type == "homogeneous" else 1
+            if mty == 1 and m.density is not None and (
+                    force_bricks or isinstance(m.density, SparseGrid)
+                    or isinstance(m.temperature, SparseGrid)):
+                self._add_medium_bricks(m, pid)
+                continue
             dens = None if m.density is None else np.ascontiguousarray(m.density, np.float32)
             temp = None if m.temperature is None else np.ascontiguousarray(m.temperature, np.float32)
             self.native.add_medium(mty, list(m.sigma_a), list(m.sigma_s), pid,
@@ -435,6 +446,26 @@ class Scene:
         self.native.cam_medium = d.cam_medium
         self.native.finalize()
 
+    def _add_medium_bricks(self, m: MediumDesc, pid: int):
+        """Grid medium in the brick layout: density and temperature share one
+        brick table built over the union of their brick coordinates."""
+        def as_sparse(g):
+            return g if isinstance(g, SparseGrid) else SparseGrid.from_dense(g)
+        dens = as_sparse(m.density)
+        temp = None if m.temperature is None else as_sparse(m.temperature)
+        coords, dvals, tvals = dens.coords, dens.values, None
+        if temp is not None:
+            if temp.shape != dens.shape:
+                raise ValueError(f"density grid {dens.shape} and temperature grid "
+                                 f"{temp.shape} must have the same shape")
+            coords = union_coords(dens, temp)
+            dvals, tvals = dens.reindexed(coords), temp.reindexed(coords)
+            tvals = tvals.reshape(-1, 512)
+        self.native.add_medium_sparse(list(m.sigma_a), list(m.sigma_s), pid,
+                                      list(m.grid_lo), list(m.grid_hi),
+                                      list(dens.shape), coords, dvals.reshape(-1, 512),
+                                      tvals, m.scale, m.emission_scale, m.temp_scale)
+
     def _set_camera_native(self):
         c = self.desc.camera
         R = camera_matrix(c)
@@ -550,4 +581,5 @@ class Scene:
         i.update(self.bvh_stats)
         i["renderer"] = self.desc.config.renderer
         i["resolution"] = (self.width, self.height)
+        i["media"] = [dict(mi) for mi in self.native.media_info()]
         return i

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import math
 import os
+import warnings
 import xml.etree.ElementTree as ET
 from typing import Dict, List, Optional
 
@@ -20,6 +21,7 @@ import numpy as np
 from .scene import (BsdfDesc, CameraDesc, EmitterDesc, MediumDesc, ObjectDesc,
                     RenderConfig, SceneDesc)
 from .obj_loader import load_obj, load_obj_multi
+from .sparse_grid import SparseGrid
 
 RENDERER_MAP = {
     "pt": "pt", "megakernel": "pt", "pt-dynamic": "pt-dyn", "dynamic": "pt-dyn",
@@ -107,6 +109,47 @@ def _load_texture_image(path: str) -> Optional[np.ndarray]:
         from ..utils.png import read_png
         return read_png(path)
     return None  # jpg etc. unsupported offline
+
+
+# `auto` reads an .nvdb grid as bricks once the dense form of its index
+# bounding box would reach this size
+SPARSE_AUTO_BYTES = 64 << 20
+
+
+def _sparse_mode(value) -> str:
+    """Grid <medium> property `sparse` -> 'auto' | 'true' | 'false'."""
+    if isinstance(value, bool):
+        return "true" if value else "false"
+    v = str(value).strip().lower()
+    if v in ("true", "1", "yes"):
+        return "true"
+    if v in ("false", "0", "no"):
+        return "false"
+    if v == "auto":
+        return "auto"
+    raise ValueError(f"medium property sparse must be auto|true|false, got {value!r}")
+
+
+def _load_npy_grid(full: str, sparse: str):
+    a = np.load(full).astype(np.float32)
+    return SparseGrid.from_dense(a) if sparse == "true" else a
+
+
+def _load_nvdb_grid(full: str, sparse: str):
+    """-> (ndarray | SparseGrid, (world_min, world_max)) of the first grid."""
+    from .nvdb import NvdbError, peek_nvdb, read_nvdb
+    use_bricks = sparse == "true" or (
+        sparse == "auto" and peek_nvdb(full)[0]["dense_nbytes"] >= SPARSE_AUTO_BYTES)
+    if use_bricks:
+        try:
+            g = read_nvdb(full, sparse=True)[0]
+            return g["sparse"], (g["world_min"], g["world_max"])
+        except NvdbError as e:
+            if sparse == "true" or "background" not in str(e):
+                raise
+            warnings.warn(f"{full}: {e}; loading the grid dense")
+    g = read_nvdb(full)[0]
+    return g["dense"], (g["world_min"], g["world_max"])
 
 
 def parse_xml(path: str) -> SceneDesc:
@@ -226,24 +269,24 @@ def parse_xml(path: str) -> SceneDesc:
             m.sigma_s = props.get("sigma_s", (1.0,) * 3)
         else:
             # grid medium: .nvdb (NanoVDB, reference vol_grid.cu:216-342 —
-            # converted to dense on the host, hippt/scene/nvdb.py) and native
-            # .npy grids load from disk; missing file -> procedural fallback
+            # converted on the host, hippt/scene/nvdb.py) and native .npy
+            # grids load from disk; missing file -> procedural fallback.
+            # `sparse` = auto|true|false picks the voxel layout: bricks
+            # (SparseGrid) or one dense array
+            sparse = _sparse_mode(props.get("sparse", el.get("sparse", "auto")))
             dens_path = props.get("density", "")
             full = os.path.normpath(os.path.join(base, dens_path)) if dens_path else ""
             dens = None
             nvdb_bounds = None
             if full and os.path.exists(full):
                 if full.endswith(".npy"):
-                    dens = np.load(full).astype(np.float32)
+                    dens = _load_npy_grid(full, sparse)
                 elif full.endswith(".nvdb"):
-                    from .nvdb import read_nvdb
-                    g = read_nvdb(full)[0]
-                    dens = g["dense"]
-                    nvdb_bounds = (g["world_min"], g["world_max"])
+                    dens, nvdb_bounds = _load_nvdb_grid(full, sparse)
             if dens is None:
                 from .procedural import smoke_density
                 dens = smoke_density(n=96) * 12.0
-            m.density = dens * 1.0
+            m.density = dens if isinstance(dens, SparseGrid) else dens * 1.0
             albedo = props.get("albedo", (0.5,) * 3)
             m.sigma_s = tuple(albedo)
             m.sigma_a = tuple(1.0 - a for a in albedo)
@@ -251,10 +294,9 @@ def parse_xml(path: str) -> SceneDesc:
             fullt = os.path.normpath(os.path.join(base, temp_path)) if temp_path else ""
             if fullt and os.path.exists(fullt):
                 if fullt.endswith(".npy"):
-                    m.temperature = np.load(fullt).astype(np.float32)
+                    m.temperature = _load_npy_grid(fullt, sparse)
                 elif fullt.endswith(".nvdb"):
-                    from .nvdb import read_nvdb
-                    m.temperature = read_nvdb(fullt)[0]["dense"]
+                    m.temperature = _load_nvdb_grid(fullt, sparse)[0]
             # explicit grid_lo/hi win; else .nvdb world bounds; else unit cube
             if "grid_lo" in props or nvdb_bounds is None:
                 m.grid_lo = props.get("grid_lo", (0.0, 0.0, 0.0))
