@@ -38,6 +38,40 @@ static_assert(sizeof(BVH4Node) == 128, "BVH4Node must be 128 bytes");
 
 constexpr int BVH4_STACK = 64;  // >= 3 * max collapsed depth; checked at build
 
+// Tagged child word, the form traversal stacks and `cur` carry: bit31 = leaf,
+// [30:27] = prim count, [26:0] = prim base; or the plain node index.  An
+// empty slot becomes BVH4_EMPTY_W (never a node index, never a leaf word).
+constexpr uint32_t BVH4_EMPTY_W = 0x7fffffffu;
+HD uint32_t bvh4_child_word(int ch, int pc) {
+    if (ch >= 0) return (uint32_t)ch;
+    if (pc == 0) return BVH4_EMPTY_W;
+    return 0x80000000u | ((uint32_t)pc << 27) | (uint32_t)(~ch);
+}
+// w[slot] for slot in 0..3 as a two-level select over registers.  The
+// ordered walks pick the sorted child's fields with this instead of
+// indexing the node copy with the run-time slot: nd.child[keys[k] & 3]
+// forces the whole 128-byte copy into a private-memory slot — stored on
+// every visit, re-loaded once per hit child — on the dependent chain
+// between the last slab test and the next node index.
+HD uint32_t bvh4_sel4(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3,
+                      uint32_t slot) {
+    uint32_t a = (slot & 1u) ? w1 : w0;
+    uint32_t b = (slot & 1u) ? w3 : w2;
+    return (slot & 2u) ? b : a;
+}
+// Tagged word of the child in `slot` of `nd` (all node indices constant).
+// Selecting child/cnt first and tagging the one word measured faster than
+// tagging all four next to the slab tests and selecting the word
+// (profiles/README.md): the compiler sinks the four taggings behind the
+// sort, where they lengthen the chain more than the second select does.
+HD uint32_t bvh4_child_word_at(const BVH4Node& nd, uint32_t slot) {
+    int ch = (int)bvh4_sel4((uint32_t)nd.child[0], (uint32_t)nd.child[1],
+                            (uint32_t)nd.child[2], (uint32_t)nd.child[3], slot);
+    int pc = (int)bvh4_sel4((uint32_t)nd.cnt[0], (uint32_t)nd.cnt[1],
+                            (uint32_t)nd.cnt[2], (uint32_t)nd.cnt[3], slot);
+    return bvh4_child_word(ch, pc);
+}
+
 // Intersect prims [base, base+cnt) and tighten rec.  tri_only (a scene-
 // uniform scalar) skips the per-prim prim_obj sphere-bit load entirely —
 // the reference's TRIANGLE_ONLY compile flag ("10% faster", defines.cuh:
@@ -210,13 +244,8 @@ HD HitRecord ray_intersect_bvh4_ww(const BVH4Node* nodes,
             }
             uint32_t next = DONE;
             for (int k = nhit - 1; k >= 0; --k) {  // far -> near so near pops first
-                int c = (int)(keys[k] & 3u);
-                int ch = nd.child[c];
-                int pc = nd.cnt[c];
-                if (ch < 0 && pc == 0) continue;   // empty slot
-                uint32_t lo = ch < 0
-                    ? (0x80000000u | ((uint32_t)pc << 27) | (uint32_t)(~ch))
-                    : (uint32_t)ch;
+                uint32_t lo = bvh4_child_word_at(nd, keys[k] & 3u);
+                if (lo == BVH4_EMPTY_W) continue;  // empty slot
                 if (k == 0) {
                     next = lo;
                 } else {
@@ -366,6 +395,8 @@ HD bool occlusion_test_bvh4_ww(const BVH4Node* nodes,
             int pc = (int)((cur >> 27) & 0xfu);
             for (int k = 0; k < pc; ++k) {
                 int pid = base + k;
+                // (skipping this load under tri_only as bvh4_leaf_hit does
+                // was measured: +0.8%, inside the noise bar, not landed)
                 bool sph = (prim_obj[pid] & PRIM_SPHERE_BIT) != 0;
                 float u, v;
                 float t = intersect_prim(prims[pid], sph, ray, u, v);
@@ -466,7 +497,8 @@ HD HitRecord ray_intersect_bvh4q_ww(const BVH4NodeQ* nodes,
             }
             uint32_t next = DONE;
             for (int k = nhit - 1; k >= 0; --k) {
-                uint32_t lo = nd.child[keys[k] & 3u];
+                uint32_t lo = bvh4_sel4(nd.child[0], nd.child[1], nd.child[2],
+                                        nd.child[3], keys[k] & 3u);
                 if (k == 0) {
                     next = lo;
                 } else {
@@ -746,13 +778,8 @@ HD bool bvh4_walk_step(Bvh4Walk& w, const BVH4Node* nodes, const Prim* prims,
         }
         uint32_t next = BVH4_DONE_W;
         for (int k = nhit - 1; k >= 0; --k) {
-            int c = (int)(keys[k] & 3u);
-            int ch = nd.child[c];
-            int pc = nd.cnt[c];
-            if (ch < 0 && pc == 0) continue;
-            uint32_t lo = ch < 0
-                ? (0x80000000u | ((uint32_t)pc << 27) | (uint32_t)(~ch))
-                : (uint32_t)ch;
+            uint32_t lo = bvh4_child_word_at(nd, keys[k] & 3u);
+            if (lo == BVH4_EMPTY_W) continue;
             if (k == 0) {
                 next = lo;
             } else {

@@ -31,13 +31,9 @@ def pybind11_includes():
     return [pybind11.get_include()]
 
 
-def build(verbose=True):
-    py_inc = sysconfig.get_paths()["include"]
-    ext = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
-    out = ROOT / "hippt" / f"_C{ext}"
-    objdir = ROOT / "build" / "obj"
-    objdir.mkdir(parents=True, exist_ok=True)
-    incs = [f"-I{py_inc}"] + [f"-I{p}" for p in pybind11_includes()]
+def compile_flags():
+    """(cflags, ldflags) for the current environment; also what
+    scripts/kernel_resources.py compiles the device code with."""
     cflags = [
         "-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}",
         "-ffast-math", "-fno-finite-math-only",
@@ -59,6 +55,17 @@ def build(verbose=True):
         # when imported into a stock (non-ASAN) python.
         cflags += ["-fsanitize=address", "-shared-libasan"]
         ldflags += ["-fsanitize=address", "-shared-libasan"]
+    return cflags, ldflags
+
+
+def build(verbose=True):
+    py_inc = sysconfig.get_paths()["include"]
+    ext = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
+    out = ROOT / "hippt" / f"_C{ext}"
+    objdir = ROOT / "build" / "obj"
+    objdir.mkdir(parents=True, exist_ok=True)
+    incs = [f"-I{py_inc}"] + [f"-I{p}" for p in pybind11_includes()]
+    cflags, ldflags = compile_flags()
     # the .o mtime cache is invalid when the flag set changes: stamp it
     stamp = objdir / ".flags"
     flags_now = " ".join(cflags)
