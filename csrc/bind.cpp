@@ -699,6 +699,12 @@ struct SceneHolder {
         dev_sv.cam_medium = cam_medium;
         if (renderer == R_WAVEFRONT_PT) {
             if (!wf) {
+                if ((long long)cam.w * cam.h > WF_MAX_PIXELS)
+                    throw std::runtime_error(
+                        "wavefront renderer: " + std::to_string(cam.w) + "x" +
+                        std::to_string(cam.h) + " exceeds the limit of " +
+                        std::to_string(WF_MAX_PIXELS) +
+                        " pixels (2^24, the 24-bit payload id of a sort entry)");
                 wf = wf_create(cam.w, cam.h);
                 if (!wf) throw std::runtime_error("wavefront state allocation failed");
             }
@@ -710,6 +716,59 @@ struct SceneHolder {
         HIP_OK(launch_render(dev_sv, (float*)accum_ptr, (float*)var_ptr, spp0, nspp, seed,
                              renderer, spec_constraint, caustic_scaling, (void*)stream, y0, y1,
                              (const uint8_t*)spp_map_ptr, (float*)aux_ptr));
+    }
+
+    // Closest hit + any-hit verdict for caller-supplied rays through the
+    // entry points every renderer uses (scene_intersect / scene_occluded):
+    // on host_sv (device < 0) or on the uploaded scene in the wavefront
+    // kernels' LDS layout.  Returns (t, prim, u, v, occluded, (lds_n, n_cached)).
+    py::tuple trace_rays(farr o, farr d, farr tmax, int device, int lds_n, int n_cached) {
+        if (o.ndim() != 2 || o.shape(1) != 3 || d.ndim() != 2 || d.shape(1) != 3 ||
+            tmax.ndim() != 1 || d.shape(0) != o.shape(0) || tmax.shape(0) != o.shape(0))
+            throw std::runtime_error("trace_rays: o (n,3), d (n,3), tmax (n,)");
+        const int n = (int)o.shape(0);
+        farr t_out(n), u_out(n), v_out(n);
+        iarr p_out(n), occ_out(n);
+        int plan[2] = {0, 0};
+        if (n == 0) return py::make_tuple(t_out, p_out, u_out, v_out, occ_out,
+                                          py::make_tuple(0, 0));
+        if (device < 0) {
+            finalize();
+            if (host_sv.n_nodes4 <= 0) throw std::runtime_error("trace_rays: empty scene");
+            for (int i = 0; i < n; ++i) {
+                Ray r;
+                r.o = {o.at(i, 0), o.at(i, 1), o.at(i, 2)};
+                r.d = {d.at(i, 0), d.at(i, 1), d.at(i, 2)};
+                HitRecord h = scene_intersect(host_sv, r, tmax.at(i));
+                t_out.mutable_at(i) = h.t;
+                u_out.mutable_at(i) = h.u;
+                v_out.mutable_at(i) = h.v;
+                p_out.mutable_at(i) = h.prim_idx;
+                occ_out.mutable_at(i) = scene_occluded(host_sv, r, tmax.at(i)) ? 1 : 0;
+            }
+        } else {
+            if (!has_dev) throw std::runtime_error("scene not uploaded to device");
+            std::vector<float> ro((size_t)n * 4), rd((size_t)n * 4, 0.f), hit((size_t)n * 4);
+            for (int i = 0; i < n; ++i) {
+                for (int c = 0; c < 3; ++c) {
+                    ro[(size_t)i * 4 + c] = o.at(i, c);
+                    rd[(size_t)i * 4 + c] = d.at(i, c);
+                }
+                ro[(size_t)i * 4 + 3] = tmax.at(i);
+            }
+            HIP_OK(wf_trace_probe(dev_sv, ro.data(), rd.data(), n, lds_n, n_cached,
+                                  hit.data(), occ_out.mutable_data(), plan));
+            for (int i = 0; i < n; ++i) {
+                t_out.mutable_at(i) = hit[(size_t)i * 4 + 0];
+                u_out.mutable_at(i) = hit[(size_t)i * 4 + 1];
+                v_out.mutable_at(i) = hit[(size_t)i * 4 + 2];
+                int32_t pi;
+                std::memcpy(&pi, &hit[(size_t)i * 4 + 3], 4);
+                p_out.mutable_at(i) = pi;
+            }
+        }
+        return py::make_tuple(t_out, p_out, u_out, v_out, occ_out,
+                              py::make_tuple(plan[0], plan[1]));
     }
 
     py::dict info() {
@@ -997,6 +1056,9 @@ PYBIND11_MODULE(_C, m) {
              py::arg("caustic_scaling"), py::arg("stream"),
              py::arg("y0") = 0, py::arg("y1") = 0, py::arg("spp_map_ptr") = 0,
              py::arg("aux_ptr") = 0)
+        .def("trace_rays", &SceneHolder::trace_rays, py::arg("o"), py::arg("d"),
+             py::arg("tmax"), py::arg("device"), py::arg("lds_n") = -1,
+             py::arg("n_cached") = -1)
         .def("info", &SceneHolder::info);
 
     m.def("build_bvh", &py_build_bvh, py::arg("prims"), py::arg("prim_obj"),
@@ -1016,6 +1078,16 @@ PYBIND11_MODULE(_C, m) {
           py::arg("ray_o"), py::arg("ray_d"), py::arg("tmax"),
           py::arg("nodes8") = farr());
 
+    m.def("wf_sort_probe", [](uarr status, uarr gather, int mode) {
+        if (status.ndim() != 1 || gather.ndim() != 1)
+            throw std::runtime_error("wf_sort_probe: status (n,), gather (m,) or empty");
+        const int n = (int)status.shape(0), m = (int)gather.shape(0);
+        uarr out(n);
+        int live = -1;
+        HIP_OK(wf_sort_probe(status.data(), n, gather.data(), m, mode,
+                             out.mutable_data(), &live));
+        return py::make_tuple(out, live);
+    }, py::arg("status"), py::arg("gather"), py::arg("mode"));
     m.def("dev_synchronize", [] { HIP_OK(dev_synchronize()); });
     m.def("dev_set_device", [](int d) { HIP_OK(dev_set_device(d)); });
 

@@ -32,10 +32,27 @@ int launch_render(const SceneView& sv, float* accum, float* var,
 
 // Wavefront path tracer (SoA queues + compaction); state owned by WfState.
 struct WfState;
-WfState* wf_create(int width, int height);
+// payload (pixel) ids ride in the low 24 bits of every sort entry
+constexpr int WF_MAX_PIXELS = 1 << 24;
+WfState* wf_create(int width, int height);   // null above WF_MAX_PIXELS pixels
 void wf_destroy(WfState* s);
 int launch_render_wavefront(WfState* st, const SceneView& sv, float* accum, float* var,
                             int spp0, int nspp, uint32_t seed, int sort_mode, void* stream);
+
+// Test probes (host pointers in and out; tests/test_gpu_probe.py).
+// wf_sort_probe runs the renderer's sort pass once: over status[0..n), or
+// over status[gather[k] & 0xFFFFFF], k in [0, m), when m > 0.  out[n] is
+// pre-filled with 0xFFFFFFFF; the live entries land in out[0..*live).
+int wf_sort_probe(const uint32_t* status, int n, const uint32_t* gather, int m,
+                  int mode, uint32_t* out, int* live);
+// wf_trace_probe runs scene_intersect + scene_occluded for n rays (ray_o_tmax:
+// n x (ox, oy, oz, tmax); ray_d: n x (dx, dy, dz, -)) in the production LDS
+// layout.  lds_n / n_cached < 0 take the render launcher's own values;
+// explicit ones pass through the launcher's clamps.  hit_out: n x (t, u, v,
+// prim as int bits); occ_out: n; plan_out: the (lds_n, n_cached) used.
+int wf_trace_probe(const SceneView& sv, const float* ray_o_tmax, const float* ray_d,
+                   int n, int lds_n, int n_cached, float* hit_out, int* occ_out,
+                   int* plan_out);
 
 // device helpers used by bind.cpp
 int dev_malloc(void** p, size_t n);

@@ -218,6 +218,23 @@ void k_sort_scatter(const uint32_t* __restrict__ in, const uint32_t* __restrict_
     }
 }
 
+// One whole sort pass: zero the 256 bins, histogram, scan (writes the live
+// count to live_dev), scatter the live entries into `out`.  Scans
+// status[0..scan_n) directly, or status[gather[k] & 0xFFFFFF] for k in
+// [0, scan_n) when `gather` is non-null.  Shared by the render loop and
+// wf_sort_probe, so the probe tests exactly what the renderer launches.
+static void wf_sort_launch(const uint32_t* status, const uint32_t* gather, int scan_n,
+                           uint32_t* hist, int* live_dev, uint32_t* out, int sort_mode,
+                           hipStream_t hs) {
+    const int nb = (scan_n + SORT_BLOCK * SORT_ITEMS - 1) / (SORT_BLOCK * SORT_ITEMS);
+    (void)hipMemsetAsync(hist, 0, 256 * sizeof(uint32_t), hs);
+    hipLaunchKernelGGL(k_sort_hist, dim3(nb), dim3(SORT_BLOCK), 0, hs,
+                       status, gather, scan_n, hist, sort_mode);
+    hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(256), 0, hs, hist, live_dev);
+    hipLaunchKernelGGL(k_sort_scatter, dim3(nb), dim3(SORT_BLOCK), 0, hs,
+                       status, gather, scan_n, hist, out, sort_mode);
+}
+
 // ----------------------------------------------------------- bounce shade
 // NEE + emitter-hit MIS + BSDF sample for live rays (current hit record).
 __global__ __launch_bounds__(256)
@@ -643,6 +660,8 @@ template <typename T>
 static int wf_alloc(T** p, size_t count) { return (int)hipMalloc((void**)p, count * sizeof(T)); }
 
 WfState* wf_create(int width, int height) {
+    // payload ids are the low 24 bits of every status / order entry
+    if ((long long)width * height > WF_MAX_PIXELS) return nullptr;
     WfState* s = new WfState();
     s->w = width; s->h = height; s->n = width * height;
     s->nb_sort = (s->n + SORT_BLOCK * SORT_ITEMS - 1) / (SORT_BLOCK * SORT_ITEMS);
@@ -680,6 +699,53 @@ void wf_destroy(WfState* s) {
     delete s;
 }
 
+// HIPPT_WF_OCC = exact waves/SIMD for the traversal kernels (both the
+// amdgpu_waves_per_eu instantiation — frees 512/occ VGPRs so the walk
+// state does not spill — AND the matching LDS block budget).  Default 4,
+// the megakernel's measured best.
+static int wf_occ() {
+    static int occ_v = [] {
+        const char* e = getenv("HIPPT_WF_OCC");
+        int occ = e ? atoi(e) : 4;   // span>=4 ladder: occ4 143-146 vs occ3 136
+        return occ < 3 ? 3 : (occ > 6 ? 6 : occ);
+    }();
+    return occ_v;
+}
+
+// Dynamic-LDS plan of every traversal kernel here (see wf_lds_ctx): the
+// block budget follows the occupancy, the top-tree cache takes its share
+// first and the stacks get the rest.  HIPPT_WF_STACK=scratch disables the
+// LDS stack + cache entirely (A/B hook).  lds_req / cache_in >= 0 replace
+// the launcher's own choice (ray probe) and pass through the same clamps.
+struct WfLdsPlan { int lds_n, n_cached; uint32_t shmem; };
+static WfLdsPlan wf_lds_plan(const SceneView& sv, int lds_req = -1, int cache_in = -1) {
+    const int occ_v = wf_occ();
+    static int lds_budget = [occ_v] {
+        const char* e = getenv("HIPPT_WF_STACK");
+        if (e && strcmp(e, "scratch") == 0) return 0;
+        return (occ_v == 3 ? 26 : occ_v == 4 ? 20 : occ_v == 5 ? 16 : 12) * WF_BLOCK * 8;
+    }();
+    // LDS top-tree cache shares the block budget with the stacks (same
+    // occupancy, fewer LDS stack entries; overflow spills to scratch)
+    static int cache_env = [] {
+        const char* e = getenv("HIPPT_TOPCACHE");
+        return e ? atoi(e) : -1;
+    }();
+    int cache_req = cache_in >= 0 ? (cache_in < sv.n_nodes4 ? cache_in : sv.n_nodes4)
+                  : cache_env >= 0 ? cache_env
+                  : (sv.cache_nodes > 0 ? sv.cache_nodes : 64);
+    if (cache_req * (int)sizeof(TravNode) > lds_budget - 4 * WF_BLOCK * 8)
+        cache_req = (lds_budget - 4 * WF_BLOCK * 8) / (int)sizeof(TravNode);
+    WfLdsPlan p;
+    p.n_cached = lds_budget > 0
+        ? (cache_req < sv.n_nodes4 ? cache_req : sv.n_nodes4) : 0;
+    const int lds_max = lds_budget > 0
+        ? (lds_budget - p.n_cached * (int)sizeof(TravNode)) / (WF_BLOCK * 8) : 0;
+    p.lds_n = lds_req >= 0 && lds_req < lds_max ? lds_req : lds_max;
+    p.shmem = (uint32_t)(p.lds_n * WF_BLOCK * 8 + p.n_cached * (int)sizeof(TravNode));
+    return p;
+}
+
 int launch_render_wavefront(WfState* st, const SceneView& sv, float* accum, float* var,
                             int spp0, int nspp, uint32_t seed, int sort_mode, void* stream) {
     if (sort_mode < 0 || sort_mode > 1) sort_mode = 0;
@@ -692,16 +758,7 @@ int launch_render_wavefront(WfState* st, const SceneView& sv, float* accum, floa
     const int n = st->n;
     dim3 blk(WF_BLOCK);
     dim3 grd_n((n + WF_BLOCK - 1) / WF_BLOCK);
-    // HIPPT_WF_OCC = exact waves/SIMD for the traversal kernels (both the
-    // amdgpu_waves_per_eu instantiation — frees 512/occ VGPRs so the walk
-    // state does not spill — AND the matching LDS block budget).  Default 4,
-    // the megakernel's measured best.  HIPPT_WF_STACK=scratch disables the
-    // LDS stack + cache entirely (A/B hook).
-    static int occ_v = [] {
-        const char* e = getenv("HIPPT_WF_OCC");
-        int occ = e ? atoi(e) : 4;   // span>=4 ladder: occ4 143-146 vs occ3 136
-        return occ < 3 ? 3 : (occ > 6 ? 6 : occ);
-    }();
+    static const int occ_v = wf_occ();
     using RaygenFn = void (*)(SceneView, WfState, int, uint32_t, int, int);
     using PrimaryFn = void (*)(SceneView, WfState, int, uint32_t, int, int, int, int);
     using TraceFn = void (*)(SceneView, WfState, const uint32_t*, int, int, int);
@@ -738,26 +795,10 @@ int launch_render_wavefront(WfState* st, const SceneView& sv, float* accum, floa
     }();
     static ShadowFn f_shadow = occ_v == 3 ? k_wf_shadow<3> : occ_v == 4 ? k_wf_shadow<4>
                              : occ_v == 5 ? k_wf_shadow<5> : k_wf_shadow<6>;
-    static int lds_budget = [] {
-        const char* e = getenv("HIPPT_WF_STACK");
-        if (e && strcmp(e, "scratch") == 0) return 0;
-        return (occ_v == 3 ? 26 : occ_v == 4 ? 20 : occ_v == 5 ? 16 : 12) * WF_BLOCK * 8;
-    }();
-    // LDS top-tree cache shares the block budget with the stacks (same
-    // occupancy, fewer LDS stack entries; overflow spills to scratch)
-    static int cache_env = [] {
-        const char* e = getenv("HIPPT_TOPCACHE");
-        return e ? atoi(e) : -1;
-    }();
-    int cache_req = cache_env >= 0 ? cache_env
-                  : (sv.cache_nodes > 0 ? sv.cache_nodes : 64);
-    if (cache_req * (int)sizeof(TravNode) > lds_budget - 4 * WF_BLOCK * 8)
-        cache_req = (lds_budget - 4 * WF_BLOCK * 8) / (int)sizeof(TravNode);
-    const int n_cached = lds_budget > 0
-        ? (cache_req < sv.n_nodes4 ? cache_req : sv.n_nodes4) : 0;
-    const int lds_n = lds_budget > 0
-        ? (lds_budget - n_cached * (int)sizeof(TravNode)) / (WF_BLOCK * 8) : 0;
-    const uint32_t shmem = (uint32_t)(lds_n * WF_BLOCK * 8 + n_cached * (int)sizeof(TravNode));
+    const WfLdsPlan plan = wf_lds_plan(sv);
+    const int n_cached = plan.n_cached;
+    const int lds_n = plan.lds_n;
+    const uint32_t shmem = plan.shmem;
     static int wf_dual = [] {
         const char* e = getenv("HIPPT_WF_DUAL");
         return e ? atoi(e) : 0;
@@ -801,14 +842,8 @@ int launch_render_wavefront(WfState* st, const SceneView& sv, float* accum, floa
         uint32_t* order_prev = st->order2;
         for (int bounce = bounce0; bounce < n_stage; bounce += (wf_fuse ? wf_span : 1)) {
             const int scan_n = prev_live;
-            const int nb = (scan_n + SORT_BLOCK * SORT_ITEMS - 1) / (SORT_BLOCK * SORT_ITEMS);
-            (void)hipMemsetAsync(st->hist, 0, 256 * sizeof(uint32_t), hs);
-            hipLaunchKernelGGL(k_sort_hist, dim3(nb), dim3(SORT_BLOCK), 0, hs,
-                               st->status, gather, scan_n, st->hist, sort_mode);
-            hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(256), 0, hs,
-                               st->hist, st->live_dev);
-            hipLaunchKernelGGL(k_sort_scatter, dim3(nb), dim3(SORT_BLOCK), 0, hs,
-                               st->status, gather, scan_n, st->hist, order_cur, sort_mode);
+            wf_sort_launch(st->status, gather, scan_n, st->hist, st->live_dev,
+                           order_cur, sort_mode, hs);
             (void)hipMemcpyAsync(st->live_host, st->live_dev, sizeof(int),
                                  hipMemcpyDeviceToHost, hs);
             int err = (int)hipStreamSynchronize(hs);
@@ -854,6 +889,94 @@ int launch_render_wavefront(WfState* st, const SceneView& sv, float* accum, floa
         hipLaunchKernelGGL(k_wf_splat, grd_n, blk, 0, hs, sv, *st, accum, var, 1);
     }
     return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------ test probes
+// Host entry points that run the production sort pass / traversal entry
+// points on caller-supplied data, with no camera or framebuffer, so tests
+// can compare them with plain references (tests/test_gpu_probe.py).
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    int alloc(size_t count) { return (int)hipMalloc((void**)&p, (count ? count : 1) * sizeof(T)); }
+};
+
+int wf_sort_probe(const uint32_t* status, int n, const uint32_t* gather, int m,
+                  int mode, uint32_t* out, int* live) {
+    if (n <= 0 || n > WF_MAX_PIXELS || m < 0 || m > n || (mode != 0 && mode != 1))
+        return (int)hipErrorInvalidValue;
+    for (int k = 0; k < m; ++k)   // the gather view indexes status: keep it in range
+        if ((gather[k] & 0x00FFFFFFu) >= (uint32_t)n) return (int)hipErrorInvalidValue;
+    DevBuf<uint32_t> d_status, d_gather, d_out, d_hist;
+    DevBuf<int> d_live;
+    int e = 0;
+    e |= d_status.alloc(n);
+    e |= d_gather.alloc(m);
+    e |= d_out.alloc(n);
+    e |= d_hist.alloc(256);
+    e |= d_live.alloc(1);
+    if (e) return e;
+    e |= (int)hipMemcpy(d_status.p, status, (size_t)n * 4, hipMemcpyHostToDevice);
+    if (m > 0) e |= (int)hipMemcpy(d_gather.p, gather, (size_t)m * 4, hipMemcpyHostToDevice);
+    e |= (int)hipMemset(d_out.p, 0xFF, (size_t)n * 4);
+    e |= (int)hipMemset(d_live.p, 0xFF, sizeof(int));
+    if (e) return e;
+    wf_sort_launch(d_status.p, m > 0 ? d_gather.p : nullptr, m > 0 ? m : n, d_hist.p,
+                   d_live.p, d_out.p, mode, nullptr);
+    e |= (int)hipGetLastError();
+    e |= (int)hipDeviceSynchronize();
+    if (e) return e;
+    e |= (int)hipMemcpy(out, d_out.p, (size_t)n * 4, hipMemcpyDeviceToHost);
+    e |= (int)hipMemcpy(live, d_live.p, sizeof(int), hipMemcpyDeviceToHost);
+    return e;
+}
+
+// One ray per thread through the production LDS layout: closest hit and
+// any-hit verdict of the same ray, via the entry points every renderer uses.
+__global__ __launch_bounds__(256)
+void k_wf_ray_probe(SceneView sv, const float4* __restrict__ ray_o,
+                    const float4* __restrict__ ray_d, int n,
+                    float4* __restrict__ hit_out, int* __restrict__ occ_out,
+                    int lds_n, int n_cached) {
+    extern __shared__ uint64_t s_stk[];
+    TravCtx tc = wf_lds_ctx(sv, s_stk, lds_n, n_cached);
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float4 o4 = ray_o[i], d4 = ray_d[i];   // o.w = tmax
+    Ray ray(Vec3(o4.x, o4.y, o4.z), Vec3(d4.x, d4.y, d4.z));
+    HitRecord hit = scene_intersect(sv, ray, o4.w, tc);
+    hit_out[i] = make_float4(hit.t, hit.u, hit.v, int_as_float(hit.prim_idx));
+    occ_out[i] = scene_occluded(sv, ray, o4.w, tc) ? 1 : 0;
+}
+
+int wf_trace_probe(const SceneView& sv, const float* ray_o_tmax, const float* ray_d,
+                   int n, int lds_n, int n_cached, float* hit_out, int* occ_out,
+                   int* plan_out) {
+    if (n <= 0 || sv.n_nodes4 <= 0) return (int)hipErrorInvalidValue;
+    const WfLdsPlan plan = wf_lds_plan(sv, lds_n, n_cached);
+    plan_out[0] = plan.lds_n;
+    plan_out[1] = plan.n_cached;
+    DevBuf<float4> d_o, d_d, d_hit;
+    DevBuf<int> d_occ;
+    int e = 0;
+    e |= d_o.alloc(n);
+    e |= d_d.alloc(n);
+    e |= d_hit.alloc(n);
+    e |= d_occ.alloc(n);
+    if (e) return e;
+    e |= (int)hipMemcpy(d_o.p, ray_o_tmax, (size_t)n * 16, hipMemcpyHostToDevice);
+    e |= (int)hipMemcpy(d_d.p, ray_d, (size_t)n * 16, hipMemcpyHostToDevice);
+    if (e) return e;
+    hipLaunchKernelGGL(k_wf_ray_probe, dim3((n + WF_BLOCK - 1) / WF_BLOCK), dim3(WF_BLOCK),
+                       plan.shmem, nullptr, sv, d_o.p, d_d.p, n, d_hit.p, d_occ.p,
+                       plan.lds_n, plan.n_cached);
+    e |= (int)hipGetLastError();
+    e |= (int)hipDeviceSynchronize();
+    if (e) return e;
+    e |= (int)hipMemcpy(hit_out, d_hit.p, (size_t)n * 16, hipMemcpyDeviceToHost);
+    e |= (int)hipMemcpy(occ_out, d_occ.p, (size_t)n * 4, hipMemcpyDeviceToHost);
+    return e;
 }
 
 } // namespace hippt

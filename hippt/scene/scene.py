@@ -348,8 +348,10 @@ class Scene:
 
         self.native.set_geometry(prims, attrs, prim_obj, nodes, nodes4, nodes8)
         self.native.set_objects(objs)
+        # `order`: reordered prim index -> index in the concatenated objects
+        # (spatial splits may reference one source prim more than once)
         self._np = dict(prims=prims, attrs=attrs, prim_obj=prim_obj, nodes=nodes,
-                        nodes4=nodes4, objs=objs)
+                        nodes4=nodes4, objs=objs, order=np.asarray(order))
 
         # ---- emitters (+ per-emitter area CDF over reordered prims)
         eprims: List[int] = []
@@ -479,6 +481,26 @@ class Scene:
     def upload(self, device: int = 0):
         self.native.upload(device)
         self._uploaded_device = device
+
+    def trace_rays(self, o, d, tmax, device: int = -1, lds_n: int = -1,
+                   n_cached: int = -1):
+        """Closest hit and any-hit verdict for explicit rays, through the
+        traversal entry points every renderer uses; no camera or frame
+        buffer involved.  device=-1 walks on the host, device>=0 on that
+        GPU in the wavefront kernels' LDS layout, where lds_n (LDS stack
+        entries per thread) and n_cached (top-tree nodes kept in LDS)
+        default to the render launcher's own values (-1) and explicit
+        values pass through its clamps.  Returns (t, prim, u, v, occluded);
+        prim indexes the BVH-ordered primitive array, -1 on a miss."""
+        o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+        tmax = np.ascontiguousarray(tmax, np.float32).reshape(-1)
+        if device >= 0 and self._uploaded_device != device:
+            self.upload(device)
+        t, prim, u, v, occ, plan = self.native.trace_rays(o, d, tmax, device,
+                                                          lds_n, n_cached)
+        self.last_trace_plan = tuple(plan)   # (lds_n, n_cached) actually used
+        return t, prim, u, v, occ.astype(bool)
 
     def update_camera(self, pos=None, lookat=None, up=None, fov=None):
         c = self.desc.camera

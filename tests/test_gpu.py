@@ -322,8 +322,14 @@ def test_wavefront_split_pipeline_env():
     """The classic per-bounce split pipeline (HIPPT_WF_FUSE=0: shade /
     shadow-queue / trace kernels + per-bounce sort) stays correct — it is
     the measured A/B baseline for the fused-span design.  Env is read at
-    first launch, so run in a subprocess."""
+    first launch, so run in a subprocess.  HIPPT_WF_TAIL=0 keeps the tail
+    kernel from taking every path over after the first sort (the default
+    threshold is far above this frame), and the [wf] log must show one sort
+    per stage: kitchen's max_depth is 10, so bounces 0..10, the last of
+    which finds no live ray (a path ends once it has bounced max_depth
+    times, as in the megakernel)."""
     import os
+    import re
     import subprocess
     import sys
     code = (
@@ -338,12 +344,19 @@ def test_wavefront_split_pipeline_env():
         "ratio = img[..., :3].mean() / p[..., :3].mean()\n"
         "assert 0.9 < ratio < 1.1, ratio\n"
         "print('split ok', ratio)\n")
-    env = dict(os.environ, HIPPT_WF_FUSE="0", HIPPT_WF_SPAN="1")
+    env = dict(os.environ, HIPPT_WF_FUSE="0", HIPPT_WF_SPAN="1",
+               HIPPT_WF_TAIL="0", HIPPT_WF_LOG="1")
     out = subprocess.run([sys.executable, "-c", code], capture_output=True,
                          text=True, timeout=240, env=env,
                          cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-1500:]
     assert "split ok" in out.stdout
+    lines = [(int(b), int(n)) for b, n in
+             re.findall(r"^\[wf\] spp 0 bounce (\d+) live (\d+)", out.stdout, re.M)]
+    assert [b for b, _ in lines] == list(range(11)), lines
+    live = [n for _, n in lines]
+    assert all(0 < n <= 192 * 108 for n in live[:10]) and live[10] == 0, live
+    assert all(a >= b for a, b in zip(live, live[1:])), live
 
 
 def test_xml_scenes_on_gpu():
