@@ -846,11 +846,27 @@ py::tuple py_collapse_bvh4(farr nodes) {
     return py::make_tuple(out, depth4);
 }
 
+// Same hit/miss verdict and, on a hit, the same distance as the reference
+// record (prim index may differ on exact t ties, so it is not compared).
+static bool same_hit(const HitRecord& ref, const HitRecord& h) {
+    return (h.prim_idx < 0) == (ref.prim_idx < 0) &&
+           (ref.prim_idx < 0 || fabsf(h.t - ref.t) <= 1e-5f * fmaxf(1.f, ref.t));
+}
+
+// Host stand-in for a thread's LDS stack slots: lds_n entries at the device
+// stride, so the walks' `sp < lds_n` halves of push and pop run on the CPU.
+static std::vector<uint64_t> host_lds_slots(int lds_n) {
+    if (lds_n < 0) throw std::runtime_error("lds_n must be >= 0");
+    return std::vector<uint64_t>((size_t)lds_n * BVH4_LDS_STRIDE);
+}
+
 // Traversal self-test: compare binary skip-link vs 4-wide ordered traversal
 // (closest hit t/prim and occlusion verdict) on caller-supplied rays.
+// lds_n > 0 keeps the bottom lds_n stack entries of every 4/8-wide walk in
+// a strided host buffer, as the kernels keep them in LDS.
 // Returns the number of mismatching rays.
 int py_bvh4_selftest(farr prims, uarr prim_obj, farr nodes, farr nodes4,
-                     farr ray_o, farr ray_d, float tmax, farr nodes8) {
+                     farr ray_o, farr ray_d, float tmax, farr nodes8, int lds_n) {
     const BVH8Node* n8p = (nodes8.ndim() == 2 && nodes8.shape(0) > 0)
         ? (const BVH8Node*)nodes8.data() : nullptr;
     int n_nodes = (int)nodes.shape(0);
@@ -858,6 +874,11 @@ int py_bvh4_selftest(farr prims, uarr prim_obj, farr nodes, farr nodes4,
     const BVH4Node* n4 = (const BVH4Node*)nodes4.data();
     const Prim* pr = (const Prim*)prims.data();
     const uint32_t* po = prim_obj.data();
+    std::vector<uint64_t> slots = host_lds_slots(lds_n);
+    uint64_t* lds = lds_n ? slots.data() : nullptr;
+    // the dual walk halves the slots the way k_wf_trace_dual does
+    const int lds_half = lds_n / 2;
+    uint64_t* lds1 = lds_n ? lds + (size_t)lds_half * BVH4_LDS_STRIDE : nullptr;
     int bad = 0;
     int nr = (int)ray_o.shape(0);
     for (int i = 0; i < nr; ++i) {
@@ -865,62 +886,61 @@ int py_bvh4_selftest(farr prims, uarr prim_obj, farr nodes, farr nodes4,
         r.o = {ray_o.at(i, 0), ray_o.at(i, 1), ray_o.at(i, 2)};
         r.d = {ray_d.at(i, 0), ray_d.at(i, 1), ray_d.at(i, 2)};
         HitRecord a = ray_intersect_bvh(bn, n_nodes, pr, po, r, tmax);
-        HitRecord b = ray_intersect_bvh4(n4, pr, po, r, tmax);
-        HitRecord w = ray_intersect_bvh4_ww(n4, pr, po, r, tmax);
-        HitRecord w32 = ray_intersect_bvh4_ww32(n4, pr, po, r, tmax);
-        if ((w32.prim_idx < 0) != (b.prim_idx < 0) ||
-            (b.prim_idx >= 0 && fabsf(w32.t - b.t) > 1e-5f * fmaxf(1.f, b.t))) { ++bad; continue; }
-        if ((w.prim_idx < 0) != (b.prim_idx < 0) ||
-            (b.prim_idx >= 0 && fabsf(w.t - b.t) > 1e-5f * fmaxf(1.f, b.t))) { ++bad; continue; }
+        HitRecord b = ray_intersect_bvh4(n4, pr, po, r, tmax, lds, lds_n);
+        HitRecord w = ray_intersect_bvh4_ww(n4, pr, po, r, tmax, lds, lds_n);
+        if (!same_hit(b, w)) { ++bad; continue; }
         {
-            Bvh4Walk wk;
-            bvh4_walk_init(wk, r, tmax);
-            while (bvh4_walk_step(wk, n4, pr, po, nullptr, 0)) {}
-            if (wk.rec.prim_idx < 0) wk.rec.t = MAX_DIST;
-            if ((wk.rec.prim_idx < 0) != (b.prim_idx < 0) ||
-                (b.prim_idx >= 0 && fabsf(wk.rec.t - b.t) > 1e-5f * fmaxf(1.f, b.t))) { ++bad; continue; }
+            // two walks of the same ray in lockstep, each on its half
+            Bvh4Walk wk0, wk1;
+            bvh4_walk_init(wk0, r, tmax);
+            bvh4_walk_init(wk1, r, tmax);
+            bool r0 = true, r1 = true;
+            while (r0 || r1) {
+                if (r0) r0 = bvh4_walk_step(wk0, n4, pr, po, lds, lds_half);
+                if (r1) r1 = bvh4_walk_step(wk1, n4, pr, po, lds1, lds_half);
+            }
+            if (wk0.rec.prim_idx < 0) wk0.rec.t = MAX_DIST;
+            if (wk1.rec.prim_idx < 0) wk1.rec.t = MAX_DIST;
+            if (!same_hit(b, wk0.rec) || !same_hit(b, wk1.rec)) { ++bad; continue; }
         }
         if (n8p) {
-            HitRecord w8 = ray_intersect_bvh8_ww(n8p, pr, po, r, tmax);
-            bool occ8 = occlusion_test_bvh8(n8p, pr, po, r, tmax);
-            bool occ_ref = occlusion_test_bvh4(n4, pr, po, r, tmax);
-            if ((w8.prim_idx < 0) != (b.prim_idx < 0) ||
-                (b.prim_idx >= 0 && fabsf(w8.t - b.t) > 1e-5f * fmaxf(1.f, b.t)) ||
-                occ8 != occ_ref) { ++bad; continue; }
+            HitRecord w8 = ray_intersect_bvh8_ww(n8p, pr, po, r, tmax, lds, lds_n);
+            bool occ8 = occlusion_test_bvh8(n8p, pr, po, r, tmax, lds, lds_n);
+            bool occ_ref = occlusion_test_bvh4(n4, pr, po, r, tmax, lds, lds_n);
+            if (!same_hit(b, w8) || occ8 != occ_ref) { ++bad; continue; }
         }
         bool occ_a = occlusion_test_bvh(bn, n_nodes, pr, po, r, tmax);
-        bool occ_b = occlusion_test_bvh4(n4, pr, po, r, tmax);
-        if (occlusion_test_bvh4_ww(n4, pr, po, r, tmax) != occ_b) { ++bad; continue; }
-        // prim index may differ only on exact t ties; compare t and object
-        bool hit_match = (a.prim_idx < 0) == (b.prim_idx < 0) &&
-                         (a.prim_idx < 0 || fabsf(a.t - b.t) <= 1e-5f * fmaxf(1.f, a.t));
-        if (!hit_match || occ_a != occ_b) ++bad;
+        bool occ_b = occlusion_test_bvh4(n4, pr, po, r, tmax, lds, lds_n);
+        if (occlusion_test_bvh4_ww(n4, pr, po, r, tmax, lds, lds_n) != occ_b) { ++bad; continue; }
+        if (!same_hit(a, b) || occ_a != occ_b) ++bad;
     }
     return bad;
 }
 
 // Quantized-walk self-test: the Q tree must agree with the fp32 walk on
 // hit/miss, occlusion, and hit distance (quantized boxes are conservative,
-// so the same closest prim must be found).  Returns mismatch count.
+// so the same closest prim must be found).  lds_n as in bvh4_selftest.
+// Returns mismatch count.
 int py_bvh4q_selftest(farr prims, uarr prim_obj, farr nodes4,
-                      farr ray_o, farr ray_d, float tmax) {
+                      farr ray_o, farr ray_d, float tmax, int lds_n) {
     const BVH4Node* n4 = (const BVH4Node*)nodes4.data();
     int nn = (int)nodes4.shape(0);
     std::vector<BVH4NodeQ> q = quantize_bvh4(n4, nn);
     const Prim* pr = (const Prim*)prims.data();
     const uint32_t* po = prim_obj.data();
+    std::vector<uint64_t> slots = host_lds_slots(lds_n);
+    uint64_t* lds = lds_n ? slots.data() : nullptr;
     int bad = 0;
     int nr = (int)ray_o.shape(0);
     for (int i = 0; i < nr; ++i) {
         Ray r;
         r.o = {ray_o.at(i, 0), ray_o.at(i, 1), ray_o.at(i, 2)};
         r.d = {ray_d.at(i, 0), ray_d.at(i, 1), ray_d.at(i, 2)};
-        HitRecord a = ray_intersect_bvh4_ww(n4, pr, po, r, tmax);
-        HitRecord b = ray_intersect_bvh4q_ww(q.data(), pr, po, r, tmax);
-        if ((a.prim_idx < 0) != (b.prim_idx < 0) ||
-            (a.prim_idx >= 0 && fabsf(a.t - b.t) > 1e-5f * fmaxf(1.f, a.t))) { ++bad; continue; }
-        bool oa = occlusion_test_bvh4_ww(n4, pr, po, r, tmax);
-        bool ob = occlusion_test_bvh4q_ww(q.data(), pr, po, r, tmax);
+        HitRecord a = ray_intersect_bvh4_ww(n4, pr, po, r, tmax, lds, lds_n);
+        HitRecord b = ray_intersect_bvh4q_ww(q.data(), pr, po, r, tmax, lds, lds_n);
+        if (!same_hit(a, b)) { ++bad; continue; }
+        bool oa = occlusion_test_bvh4_ww(n4, pr, po, r, tmax, lds, lds_n);
+        bool ob = occlusion_test_bvh4q_ww(q.data(), pr, po, r, tmax, lds, lds_n);
         if (oa != ob) ++bad;
     }
     return bad;
@@ -1072,11 +1092,11 @@ PYBIND11_MODULE(_C, m) {
     m.def("env_check", &py_env_check);
     m.def("bvh4q_selftest", &py_bvh4q_selftest,
           py::arg("prims"), py::arg("prim_obj"), py::arg("nodes4"),
-          py::arg("ray_o"), py::arg("ray_d"), py::arg("tmax"));
+          py::arg("ray_o"), py::arg("ray_d"), py::arg("tmax"), py::arg("lds_n") = 0);
     m.def("bvh4_selftest", &py_bvh4_selftest,
           py::arg("prims"), py::arg("prim_obj"), py::arg("nodes"), py::arg("nodes4"),
           py::arg("ray_o"), py::arg("ray_d"), py::arg("tmax"),
-          py::arg("nodes8") = farr());
+          py::arg("nodes8") = farr(), py::arg("lds_n") = 0);
 
     m.def("wf_sort_probe", [](uarr status, uarr gather, int mode) {
         if (status.ndim() != 1 || gather.ndim() != 1)

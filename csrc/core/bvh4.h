@@ -1,4 +1,5 @@
-// bvh4.h — 4-wide BVH node layout + ordered short-stack traversal.
+// bvh4.h — wide BVH node layouts, the traversal pieces, and the walks built
+// from them.
 //
 // Capability parity: same traversal semantics as the binary skip-link walk in
 // bvh.h (reference src/renderer/tracing_func.cuh:44-181), but the node is
@@ -17,42 +18,101 @@
 //     and each stack entry carries t_near so stale far subtrees are culled
 //     on pop after the hit distance tightens.
 //
-// Box storage is SoA-within-node (lo_x[4], lo_y[4], ... ) so each of the 4
-// slab tests reads stride-16 floats from the same 2 cache lines.
+// Layout of this file: node types, then the pieces every walk is built from
+// (tagged child word, slab test, key build + sort, stack, leaf loops), each
+// written once, then the walks.
+//
+// Form of the pieces.  Pieces over scalars and the node copy are HD
+// functions.  Pieces that write the walk's private arrays or leave the walk
+// from inside a loop — key build + sort, stack push and pop, the ordered
+// node visit made of them, the any-hit leaf loop — are function-like macros
+// (BVH_*), because a function boundary there is not code-neutral: the
+// compiler simplifies a helper on its own before it inlines it, where `keys`
+// and `stack` are opaque pointers and not yet the caller's promotable
+// locals, and the walk comes out differently (as HD functions ScratchSize
+// moved in 14 of 45 kernels, e.g. k_render<0,4,false> 1216 -> 1232 B/lane;
+// scripts/kernel_resources.py).  As macros, every kernel except the
+// bvh-cost visualiser is instruction for instruction what the hand-copied
+// walks compiled to (profiles/README.md).
+//
+// Which walks a kernel can reach in the default build:
+//   ray_intersect_bvh4_ww, occlusion_test_bvh4_ww   every render kernel
+//   bvh4_walk_step                                  k_wf_trace_dual
+//   bvh4_cost                                       bvh-cost renderer only
+// Everything else is a host-tested record or A/B oracle: the inline-leaf
+// walks ray_intersect_bvh4 / occlusion_test_bvh4, the quantized *q_ww walks
+// (device code only when built with HIPPT_QBVH=1), and the 8-wide walks of
+// bvh8.h.
 #pragma once
 #include "bvh.h"
 
 namespace hippt {
 
-// 128-byte 4-wide node.
-//   child[c] >= 0 : internal child, index of a BVH4Node
+// W-wide node, 32*W bytes.  Box storage is SoA-within-node (lo_x[W],
+// lo_y[W], ...) so the W slab tests read same-stride floats from the same
+// cache lines.
+//   child[c] >= 0 : internal child, index of a node
 //   child[c] <  0 : leaf child, prim_base = ~child[c], prim count = cnt[c]
 //   cnt[c] == 0 AND child[c] == 0: empty slot (box is inverted: never hits)
-struct alignas(16) BVH4Node {
-    float lo_x[4], lo_y[4], lo_z[4];
-    float hi_x[4], hi_y[4], hi_z[4];
-    int32_t child[4];
-    int32_t cnt[4];
+// The walks apply the empty-slot rule (a leaf child of no prims is dropped)
+// after the slab test, so it is paid only for children whose box is hit.
+template <int W>
+struct alignas(16) BVHWideNode {
+    static constexpr int WIDTH = W;
+    static constexpr bool EMPTY_BEFORE_BOX = false;
+    float lo_x[W], lo_y[W], lo_z[W];
+    float hi_x[W], hi_y[W], hi_z[W];
+    int32_t child[W];
+    int32_t cnt[W];
 };
+using BVH4Node = BVHWideNode<4>;
 static_assert(sizeof(BVH4Node) == 128, "BVH4Node must be 128 bytes");
+
+// Quantized 64-byte 4-wide node (Ylitie-style child-box compression,
+// re-derived for this tree): child AABBs stored as uint8 offsets inside
+// the node's own box, power-of-two per-axis scales so decompression is
+// an fma per bound.  Quantized bounds round OUTWARD (conservative: never
+// misses a hit, a few extra visits).  Halves bytes per dependent node
+// load (1 cacheline, not 2) and doubles LDS top-cache coverage.
+// An empty slot is known by its word, before the box is dequantized.
+struct alignas(16) BVH4NodeQ {
+    static constexpr int WIDTH = 4;
+    static constexpr bool EMPTY_BEFORE_BOX = true;
+    float ox, oy, oz;        // node box origin
+    uint8_t ex, ey, ez;      // per-axis scale exponents: scale = 2^(e-127)
+    uint8_t pad;
+    uint8_t qlo[4][3];       // child lo offsets (floor)
+    uint8_t qhi[4][3];       // child hi offsets (ceil); qhi<qlo = empty slot
+    uint32_t child[4];       // tagged child words (BVH4_NONE_W for empty)
+};
+static_assert(sizeof(BVH4NodeQ) == 64, "BVH4NodeQ must be 64 bytes");
 
 constexpr int BVH4_STACK = 64;  // >= 3 * max collapsed depth; checked at build
 
-// Tagged child word, the form traversal stacks and `cur` carry: bit31 = leaf,
-// [30:27] = prim count, [26:0] = prim base; or the plain node index.  An
-// empty slot becomes BVH4_EMPTY_W (never a node index, never a leaf word).
-constexpr uint32_t BVH4_EMPTY_W = 0x7fffffffu;
-HD uint32_t bvh4_child_word(int ch, int pc) {
-    if (ch >= 0) return (uint32_t)ch;
-    if (pc == 0) return BVH4_EMPTY_W;
-    return 0x80000000u | ((uint32_t)pc << 27) | (uint32_t)(~ch);
+// ------------------------------------------------------------ tagged word
+// The form traversal stacks and `cur` carry: bit31 = leaf, [30:27] = prim
+// count (builders cap leaves at 15 prims), [26:0] = prim base (up to 134M
+// prims); or the plain node index.  BVH4_NONE_W is neither: it stands for an
+// empty child slot and for "nothing left to visit".
+constexpr uint32_t BVH4_NONE_W = 0x7fffffffu;
+HD uint32_t bvh4_filled_word(int ch, int pc) {  // of a slot known not to be empty
+    return ch < 0 ? (0x80000000u | ((uint32_t)pc << 27) | (uint32_t)(~ch)) : (uint32_t)ch;
 }
-// w[slot] for slot in 0..3 as a two-level select over registers.  The
-// ordered walks pick the sorted child's fields with this instead of
-// indexing the node copy with the run-time slot: nd.child[keys[k] & 3]
-// forces the whole 128-byte copy into a private-memory slot — stored on
-// every visit, re-loaded once per hit child — on the dependent chain
-// between the last slab test and the next node index.
+HD uint32_t bvh4_child_word(int ch, int pc) {
+    if (ch < 0 && pc == 0) return BVH4_NONE_W;  // the empty-slot rule
+    return bvh4_filled_word(ch, pc);
+}
+HD bool bvh4_is_leaf(uint32_t w) { return w >= 0x80000000u; }
+HD bool bvh4_not_leaf(uint32_t w) { return w < 0x80000000u; }  // node or NONE
+HD bool bvh4_is_node(uint32_t w) { return bvh4_not_leaf(w) && w != BVH4_NONE_W; }
+HD int bvh4_leaf_base(uint32_t w) { return (int)(w & 0x07ffffffu); }
+HD int bvh4_leaf_count(uint32_t w) { return (int)((w >> 27) & 0xfu); }
+
+// w[slot] as a select tree over registers.  The ordered walks pick the
+// sorted child's fields with this instead of indexing the node copy with the
+// run-time slot: nd.child[keys[k] & 3] forces the whole node copy into a
+// private-memory slot — stored on every visit, re-loaded once per hit child —
+// on the dependent chain between the last slab test and the next node index.
 HD uint32_t bvh4_sel4(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3,
                       uint32_t slot) {
     uint32_t a = (slot & 1u) ? w1 : w0;
@@ -64,14 +124,167 @@ HD uint32_t bvh4_sel4(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3,
 // tagging all four next to the slab tests and selecting the word
 // (profiles/README.md): the compiler sinks the four taggings behind the
 // sort, where they lengthen the chain more than the second select does.
-HD uint32_t bvh4_child_word_at(const BVH4Node& nd, uint32_t slot) {
+// (bvh8.h adds the width-8 overload.)
+HD uint32_t bvh_child_word_at(const BVH4Node& nd, uint32_t slot) {
     int ch = (int)bvh4_sel4((uint32_t)nd.child[0], (uint32_t)nd.child[1],
                             (uint32_t)nd.child[2], (uint32_t)nd.child[3], slot);
     int pc = (int)bvh4_sel4((uint32_t)nd.cnt[0], (uint32_t)nd.cnt[1],
                             (uint32_t)nd.cnt[2], (uint32_t)nd.cnt[3], slot);
     return bvh4_child_word(ch, pc);
 }
+HD uint32_t bvh_child_word_at(const BVH4NodeQ& nd, uint32_t slot) {
+    return bvh4_sel4(nd.child[0], nd.child[1], nd.child[2], nd.child[3], slot);
+}
+// Word of child c (a constant) of a slot already known not to be empty.
+template <int W>
+HD uint32_t bvh_filled_child_word(const BVHWideNode<W>& nd, int c) {
+    return bvh4_filled_word(nd.child[c], nd.cnt[c]);
+}
+HD uint32_t bvh_filled_child_word(const BVH4NodeQ& nd, int c) { return nd.child[c]; }
 
+// -------------------------------------------------------------- slab test
+// Box [lo, hi] against the ray (inv_d, o_div = o * inv_d) on [0, tmax]: the
+// ray is inside for t in [enter, exit_], which is empty on a miss.  The
+// comparison stays with the caller: the ordered walks take `enter <= exit_`
+// as a hit, the unordered ones skip on `enter > exit_`.
+HD void bvh_slab(float lx, float ly, float lz, float hx, float hy, float hz,
+                 const Vec3& inv_d, const Vec3& o_div, float tmax,
+                 float& enter, float& exit_) {
+    float t0x = fmaf(lx, inv_d.x, -o_div.x);
+    float t1x = fmaf(hx, inv_d.x, -o_div.x);
+    float t0y = fmaf(ly, inv_d.y, -o_div.y);
+    float t1y = fmaf(hy, inv_d.y, -o_div.y);
+    float t0z = fmaf(lz, inv_d.z, -o_div.z);
+    float t1z = fmaf(hz, inv_d.z, -o_div.z);
+    enter = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)),
+                  fmaxf(fminf(t0z, t1z), 0.f));
+    exit_ = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)),
+                  fminf(fmaxf(t0z, t1z), tmax));
+}
+// Child c of a node.  bvh_slot_known_empty: can the slot be skipped before
+// its box is looked at?  Never for an fp32 node (EMPTY_BEFORE_BOX is false).
+template <int W>
+HD bool bvh_slot_known_empty(const BVHWideNode<W>&, int) { return false; }
+template <int W>
+HD void bvh_child_slab(const BVHWideNode<W>& nd, int c, const Vec3& inv_d,
+                       const Vec3& o_div, float tmax, float& enter, float& exit_) {
+    bvh_slab(nd.lo_x[c], nd.lo_y[c], nd.lo_z[c], nd.hi_x[c], nd.hi_y[c], nd.hi_z[c],
+             inv_d, o_div, tmax, enter, exit_);
+}
+// scale = 2^(e-127): e chosen so extent/255 <= scale (exact for
+// power-of-two extents, <2x conservative otherwise)
+HD float bvh4q_scale(uint8_t e) {
+    return uint_as_float((uint32_t)(e) << 23);
+}
+// Quantized child: dequantized (cvt + fma per bound), then the same test.
+HD bool bvh_slot_known_empty(const BVH4NodeQ& nd, int c) { return nd.child[c] == BVH4_NONE_W; }
+HD void bvh_child_slab(const BVH4NodeQ& nd, int c, const Vec3& inv_d,
+                       const Vec3& o_div, float tmax, float& enter, float& exit_) {
+    const float sx = bvh4q_scale(nd.ex), sy = bvh4q_scale(nd.ey), sz = bvh4q_scale(nd.ez);
+    bvh_slab(fmaf((float)nd.qlo[c][0], sx, nd.ox), fmaf((float)nd.qlo[c][1], sy, nd.oy),
+             fmaf((float)nd.qlo[c][2], sz, nd.oz), fmaf((float)nd.qhi[c][0], sx, nd.ox),
+             fmaf((float)nd.qhi[c][1], sy, nd.oy), fmaf((float)nd.qhi[c][2], sz, nd.oz),
+             inv_d, o_div, tmax, enter, exit_);
+}
+
+// ---------------------------------------------------- key build and sort
+// BVH_HIT_KEYS(Node, nd, inv_d, o_div, tmax, keys, nhit): slab-test the
+// children of nd (a Node); declares keys[0..nhit) = the hit ones, nearest
+// first.  key = (t_near bits & ~(W-1)) | slot: t_near >= 0, so the float bit
+// pattern orders like the float, and the low bits carry the slot index.
+// Width 4 sorts with a network, width 8 by insertion.
+#define BVH_KEY_ORDER(a, b) \
+    if ((a) > (b)) { uint32_t t_ = (a); (a) = (b); (b) = t_; }
+#define BVH_HIT_KEYS(Node, nd, inv_d, o_div, tmax, keys, nhit)                     \
+    uint32_t keys[Node::WIDTH];                                                    \
+    int nhit = 0;                                                                  \
+    _Pragma("unroll")                                                              \
+    for (int c_ = 0; c_ < Node::WIDTH; ++c_) {                                     \
+        if (bvh_slot_known_empty(nd, c_)) continue;                                \
+        float enter_, exit_;                                                       \
+        bvh_child_slab(nd, c_, inv_d, o_div, tmax, enter_, exit_);                 \
+        if (enter_ <= exit_)                                                       \
+            keys[nhit++] = (float_as_uint(enter_) & ~(Node::WIDTH - 1u)) | (uint32_t)c_; \
+    }                                                                              \
+    if constexpr (Node::WIDTH == 4) {                                              \
+        if (nhit > 1) {                                                            \
+            BVH_KEY_ORDER(keys[0], keys[1])                                        \
+            if (nhit > 2) {                                                        \
+                BVH_KEY_ORDER(keys[1], keys[2])                                    \
+                BVH_KEY_ORDER(keys[0], keys[1])                                    \
+                if (nhit > 3) {                                                    \
+                    BVH_KEY_ORDER(keys[2], keys[3])                                \
+                    BVH_KEY_ORDER(keys[1], keys[2])                                \
+                    BVH_KEY_ORDER(keys[0], keys[1])                                \
+                }                                                                  \
+            }                                                                      \
+        }                                                                          \
+    } else {                                                                       \
+        for (int i_ = 1; i_ < nhit; ++i_) {                                        \
+            uint32_t k_ = keys[i_];                                                \
+            int j_ = i_ - 1;                                                       \
+            while (j_ >= 0 && keys[j_] > k_) { keys[j_ + 1] = keys[j_]; --j_; }    \
+            keys[j_ + 1] = k_;                                                     \
+        }                                                                          \
+    }
+
+// ------------------------------------------------------------------ stack
+// Bottom lds_n entries live in LDS (device kernels pass a per-thread slot
+// pointer into a __shared__ array, entry d at slot[d*256] for 256-thread
+// blocks), the rest spill to a private (scratch) overflow array.
+// Scratch-backed stacks were measured to be the BVH4 bottleneck on MI355X
+// (the walk is latency-bound; per-step 8-byte scratch push/pops thrash the
+// vector caches), and the LDS allocation doubles as the occupancy governor:
+// LDSN entries/thread x 8 B x 256 threads of LDS per block caps blocks/CU
+// exactly where the scratch walk wants to run.  On the host (lds_n = 0)
+// everything goes to the plain array.
+//
+// Ordered walks store (t_near bits << 32) | tagged word, so that on pop
+// entries whose t_near is already beyond the current hit are skipped without
+// a node load; unordered walks store the bare word.
+constexpr int BVH4_LDS_STRIDE = 256;  // all render blocks are 256 threads
+
+#define BVH_PUSH(stack, sp, lds_slot, lds_n, e)                       \
+    {                                                                 \
+        if ((sp) < (lds_n)) (lds_slot)[(sp) * BVH4_LDS_STRIDE] = (e); \
+        else (stack)[(sp) - (lds_n)] = (e);                           \
+        ++(sp);                                                       \
+    }
+// Expression: the top entry.  The stack must not be empty.
+#define BVH_POP(stack, sp, lds_slot, lds_n) \
+    (--(sp), (sp) < (lds_n) ? (lds_slot)[(sp) * BVH4_LDS_STRIDE] : (stack)[(sp) - (lds_n)])
+// cur = word of the top entry, BVH4_NONE_W if there is none.  `then_none`
+// (and `then_word` below) say how the caller goes on: break, or return.
+#define BVH_POP_WORD(cur, stack, sp, lds_slot, lds_n, then_none)           \
+    {                                                                      \
+        if ((sp) == 0) { (cur) = BVH4_NONE_W; then_none; }                 \
+        (cur) = (uint32_t)BVH_POP(stack, sp, lds_slot, lds_n);             \
+    }
+// Same, culling: entries whose subtree starts at or beyond t are dropped.
+#define BVH_POP_CLOSER(cur, stack, sp, lds_slot, lds_n, t, then_none, then_word) \
+    for (;;) {                                                                   \
+        if ((sp) == 0) { (cur) = BVH4_NONE_W; then_none; }                       \
+        uint64_t e_ = BVH_POP(stack, sp, lds_slot, lds_n);                       \
+        if (uint_as_float((uint32_t)(e_ >> 32)) < (t)) { (cur) = (uint32_t)e_; then_word; } \
+    }
+
+// Ordered visit of node nd: push the hit children far -> near (so the near
+// ones pop first); next = the nearest one's word, BVH4_NONE_W if none is hit.
+#define BVH_VISIT_ORDERED(Node, next, nd, inv_d, o_div, tmax, stack, sp, lds_slot, lds_n) \
+    BVH_HIT_KEYS(Node, nd, inv_d, o_div, tmax, keys_, nhit_)                           \
+    uint32_t next = BVH4_NONE_W;                                                       \
+    for (int k_ = nhit_ - 1; k_ >= 0; --k_) {                                          \
+        uint32_t lo_ = bvh_child_word_at(nd, keys_[k_] & (Node::WIDTH - 1u));          \
+        if (lo_ == BVH4_NONE_W) continue; /* empty slot */                             \
+        if (k_ == 0) {                                                                 \
+            next = lo_;                                                                \
+        } else {                                                                       \
+            uint64_t e_ = ((uint64_t)(keys_[k_] & ~(Node::WIDTH - 1u)) << 32) | lo_;   \
+            BVH_PUSH(stack, sp, lds_slot, lds_n, e_)                                   \
+        }                                                                              \
+    }
+
+// ------------------------------------------------------------- leaf loops
 // Intersect prims [base, base+cnt) and tighten rec.  tri_only (a scene-
 // uniform scalar) skips the per-prim prim_obj sphere-bit load entirely —
 // the reference's TRIANGLE_ONLY compile flag ("10% faster", defines.cuh:
@@ -89,19 +302,158 @@ HD void bvh4_leaf_hit(const Prim* prims, const uint32_t* prim_obj,
         }
     }
 }
+// Any-hit form: `return true` from the walk if a prim of [base, base+cnt)
+// blocks (EPSILON, tmax).  A macro because it leaves the walk from inside
+// the loop.  (Skipping the prim_obj load under tri_only as bvh4_leaf_hit
+// does was measured: +0.8%, inside the noise bar, not landed.)
+#define BVH_LEAF_ANY_RETURN(prims, prim_obj, ray, base, cnt, tmax)            \
+    for (int k_ = 0; k_ < (cnt); ++k_) {                                      \
+        int pid_ = (base) + k_;                                               \
+        bool sph_ = ((prim_obj)[pid_] & PRIM_SPHERE_BIT) != 0;                \
+        float u_, v_;                                                         \
+        float t_ = intersect_prim((prims)[pid_], sph_, ray, u_, v_);          \
+        if (t_ > EPSILON && t_ < (tmax)) return true;                         \
+    }
 
-// Traversal stack: bottom lds_n entries live in LDS (device kernels pass a
-// per-thread slot pointer into a __shared__ array, entry d at slot[d*256]
-// for 256-thread blocks), the rest spill to a private (scratch) overflow
-// array.  Scratch-backed stacks were measured to be the BVH4 bottleneck on
-// MI355X (the walk is latency-bound; per-step 8-byte scratch push/pops
-// thrash the vector caches), and the LDS allocation doubles as the
-// occupancy governor: LDSN entries/thread x 8 B x 256 threads of LDS per
-// block caps blocks/CU exactly where the scratch walk wants to run.
-// On the host (lds_n = 0) everything goes to the plain array.
-constexpr int BVH4_LDS_STRIDE = 256;  // all render blocks are 256 threads
+// ------------------------------------------------------ while-while walks
+// Aila & Laine style phase batching, re-derived for wave64: lanes alternate
+// between a node-walk phase and a leaf-test phase at the OUTER loop level,
+// so a wave tends to execute runs of same-kind work instead of interleaving
+// a node step on some lanes with prim tests on others.  Leaf children are
+// POSTPONED onto the stack (tagged entries) instead of intersected inline.
+// Measured A/B against the inline walk (divergence: VALUUtilization 15% on
+// the inline walk).
+template <class Node>
+HD HitRecord bvh_closest_ww(const Node* nodes, const Prim* prims,
+                            const uint32_t* prim_obj, const Ray& ray, float tmax,
+                            uint64_t* lds_slot, int lds_n, const Node* top_cache,
+                            int n_cached, bool tri_only) {
+    HitRecord rec;
+    rec.t = tmax;
+    const Vec3 inv_d = safe_rcp_dir(ray.d);
+    const Vec3 o_div = ray.o * inv_d;
+    uint64_t stack[BVH4_STACK];
+    int sp = 0;
+    uint32_t cur = 0;
+    for (;;) {
+        // ---- node phase: walk internal nodes until a leaf surfaces
+        while (bvh4_is_node(cur)) {
+            // top-of-tree nodes come from the LDS copy (every walk starts at
+            // the root; 95% L2 hit rate means the bound is hit LATENCY, and
+            // LDS is ~4x closer than L2).  Pointer select, single flat load.
+            const Node* nsrc = (int)cur < n_cached ? top_cache : nodes;
+            const Node nd = nsrc[cur];
+            BVH_VISIT_ORDERED(Node, next, nd, inv_d, o_div, rec.t,
+                              stack, sp, lds_slot, lds_n)
+            if (next != BVH4_NONE_W) { cur = next; continue; }
+            BVH_POP_CLOSER(cur, stack, sp, lds_slot, lds_n, rec.t, break, break)
+        }
+        if (cur == BVH4_NONE_W) break;
+        // ---- leaf phase: drain consecutive leaf entries
+        while (bvh4_is_leaf(cur)) {
+            bvh4_leaf_hit(prims, prim_obj, ray, bvh4_leaf_base(cur),
+                          bvh4_leaf_count(cur), rec, tri_only);
+            BVH_POP_CLOSER(cur, stack, sp, lds_slot, lds_n, rec.t, break, break)
+        }
+        if (cur == BVH4_NONE_W) break;
+    }
+    if (rec.prim_idx < 0) rec.t = MAX_DIST;
+    return rec;
+}
+// Any-hit form: no ordering (any hit ends the walk), the first hit child
+// continues and the others are pushed as bare words; `true` on the first
+// blocking prim.  Measured +1-2% against the inline-leaf occlusion walk; now
+// the default.
+template <class Node>
+HD bool bvh_any_ww(const Node* nodes, const Prim* prims, const uint32_t* prim_obj,
+                   const Ray& ray, float tmax, uint64_t* lds_slot, int lds_n,
+                   const Node* top_cache, int n_cached) {
+    const Vec3 inv_d = safe_rcp_dir(ray.d);
+    const Vec3 o_div = ray.o * inv_d;
+    uint64_t stack[BVH4_STACK];
+    int sp = 0;
+    uint32_t cur = 0;
+    for (;;) {
+        while (bvh4_is_node(cur)) {
+            const Node* nsrc = (int)cur < n_cached ? top_cache : nodes;
+            const Node nd = nsrc[cur];
+            uint32_t next = BVH4_NONE_W;
+#pragma unroll
+            for (int c = 0; c < Node::WIDTH; ++c) {
+                if (bvh_slot_known_empty(nd, c)) continue;
+                float enter, exit_;
+                bvh_child_slab(nd, c, inv_d, o_div, tmax, enter, exit_);
+                if (enter > exit_) continue;
+                if constexpr (!Node::EMPTY_BEFORE_BOX) {
+                    // the empty-slot rule, spelled out here: as the result of
+                    // a helper the && compiles to different code
+                    if (nd.child[c] < 0 && nd.cnt[c] == 0) continue;
+                }
+                const uint32_t lo = bvh_filled_child_word(nd, c);
+                if (next == BVH4_NONE_W) {
+                    next = lo;
+                } else {
+                    uint64_t e = (uint64_t)lo;
+                    BVH_PUSH(stack, sp, lds_slot, lds_n, e)
+                }
+            }
+            if (next != BVH4_NONE_W) { cur = next; continue; }
+            BVH_POP_WORD(cur, stack, sp, lds_slot, lds_n, break)
+        }
+        if (cur == BVH4_NONE_W) return false;
+        while (bvh4_is_leaf(cur)) {
+            const int base = bvh4_leaf_base(cur), pc = bvh4_leaf_count(cur);
+            BVH_LEAF_ANY_RETURN(prims, prim_obj, ray, base, pc, tmax)
+            BVH_POP_WORD(cur, stack, sp, lds_slot, lds_n, break)
+        }
+        if (cur == BVH4_NONE_W) return false;
+    }
+}
 
-// Closest-hit ordered traversal.
+HD HitRecord ray_intersect_bvh4_ww(const BVH4Node* nodes,
+                                   const Prim* prims, const uint32_t* prim_obj,
+                                   const Ray& ray, float tmax,
+                                   uint64_t* lds_slot = nullptr, int lds_n = 0,
+                                   const BVH4Node* top_cache = nullptr,
+                                   int n_cached = 0, bool tri_only = false) {
+    return bvh_closest_ww(nodes, prims, prim_obj, ray, tmax, lds_slot, lds_n,
+                          top_cache, n_cached, tri_only);
+}
+// (tri_only is taken for call-site symmetry; see BVH_LEAF_ANY_RETURN)
+HD bool occlusion_test_bvh4_ww(const BVH4Node* nodes,
+                               const Prim* prims, const uint32_t* prim_obj,
+                               const Ray& ray, float tmax,
+                               uint64_t* lds_slot = nullptr, int lds_n = 0,
+                               const BVH4Node* top_cache = nullptr,
+                               int n_cached = 0, bool /*tri_only*/ = false) {
+    return bvh_any_ww(nodes, prims, prim_obj, ray, tmax, lds_slot, lds_n,
+                      top_cache, n_cached);
+}
+// The same two walks over the quantized tree.
+HD HitRecord ray_intersect_bvh4q_ww(const BVH4NodeQ* nodes,
+                                    const Prim* prims, const uint32_t* prim_obj,
+                                    const Ray& ray, float tmax,
+                                    uint64_t* lds_slot = nullptr, int lds_n = 0,
+                                    const BVH4NodeQ* top_cache = nullptr,
+                                    int n_cached = 0) {
+    return bvh_closest_ww(nodes, prims, prim_obj, ray, tmax, lds_slot, lds_n,
+                          top_cache, n_cached, false);
+}
+HD bool occlusion_test_bvh4q_ww(const BVH4NodeQ* nodes,
+                                const Prim* prims, const uint32_t* prim_obj,
+                                const Ray& ray, float tmax,
+                                uint64_t* lds_slot = nullptr, int lds_n = 0,
+                                const BVH4NodeQ* top_cache = nullptr,
+                                int n_cached = 0) {
+    return bvh_any_ww(nodes, prims, prim_obj, ray, tmax, lds_slot, lds_n,
+                      top_cache, n_cached);
+}
+
+// ------------------------------------------------------ inline-leaf walks
+// Closest-hit ordered walk that intersects leaves inline, near -> far,
+// tightening rec.t before far subtrees are entered: the walk the
+// while-while form replaced on the device.  It shares the pieces but keeps a
+// body of its own, as the independent side of bvh4_selftest.
 HD HitRecord ray_intersect_bvh4(const BVH4Node* nodes,
                                 const Prim* prims, const uint32_t* prim_obj,
                                 const Ray& ray, float tmax = MAX_DIST,
@@ -110,502 +462,152 @@ HD HitRecord ray_intersect_bvh4(const BVH4Node* nodes,
     rec.t = tmax;
     const Vec3 inv_d = safe_rcp_dir(ray.d);
     const Vec3 o_div = ray.o * inv_d;
-    // stack entry: (t_near bits << 32) | node index.  t_near >= 0 so the
-    // float bit pattern orders like the float; on pop, entries whose t_near
-    // is already beyond the current hit are skipped without a node load.
     uint64_t stack[BVH4_STACK];
     int sp = 0;
-    int cur = 0;
-    while (true) {
-        const BVH4Node nd = nodes[cur];
-        // 4 independent slab tests; keys sort hit children front-to-back.
-        // key = (t_near bits & ~3) | slot — low 2 bits carry the slot index.
-        uint32_t keys[4];
-        int nhit = 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            float t0x = fmaf(nd.lo_x[c], inv_d.x, -o_div.x);
-            float t1x = fmaf(nd.hi_x[c], inv_d.x, -o_div.x);
-            float t0y = fmaf(nd.lo_y[c], inv_d.y, -o_div.y);
-            float t1y = fmaf(nd.hi_y[c], inv_d.y, -o_div.y);
-            float t0z = fmaf(nd.lo_z[c], inv_d.z, -o_div.z);
-            float t1z = fmaf(nd.hi_z[c], inv_d.z, -o_div.z);
-            float enter = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)),
-                                fmaxf(fminf(t0z, t1z), 0.f));
-            float exit_ = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)),
-                                fminf(fmaxf(t0z, t1z), rec.t));
-            if (enter <= exit_) keys[nhit++] = (float_as_uint(enter) & ~3u) | (uint32_t)c;
-        }
-        // sort up to 4 keys ascending (nearest first): sorting network
-        if (nhit > 1) {
-            if (keys[0] > keys[1]) { uint32_t t = keys[0]; keys[0] = keys[1]; keys[1] = t; }
-            if (nhit > 2) {
-                if (keys[1] > keys[2]) { uint32_t t = keys[1]; keys[1] = keys[2]; keys[2] = t; }
-                if (keys[0] > keys[1]) { uint32_t t = keys[0]; keys[0] = keys[1]; keys[1] = t; }
-                if (nhit > 3) {
-                    if (keys[2] > keys[3]) { uint32_t t = keys[2]; keys[2] = keys[3]; keys[3] = t; }
-                    if (keys[1] > keys[2]) { uint32_t t = keys[1]; keys[1] = keys[2]; keys[2] = t; }
-                    if (keys[0] > keys[1]) { uint32_t t = keys[0]; keys[0] = keys[1]; keys[1] = t; }
-                }
-            }
-        }
-        // near->far: leaves intersect inline (tightening rec.t before far
-        // subtrees are entered); internals: nearest continues, rest pushed.
-        int next = -1;
-        for (int k = 0; k < nhit; ++k) {
-            int c = (int)(keys[k] & 3u);
-            int ch = nd.child[c];
-            int pc = nd.cnt[c];
-            if (ch < 0) {
-                bvh4_leaf_hit(prims, prim_obj, ray, ~ch, pc, rec);
-            } else if (next < 0) {
-                next = ch;
-            } else {
-                uint64_t e = ((uint64_t)(keys[k] & ~3u) << 32) | (uint32_t)ch;
-                if (sp < lds_n) lds_slot[sp * BVH4_LDS_STRIDE] = e;
-                else stack[sp - lds_n] = e;
-                ++sp;
-            }
-        }
-        if (next >= 0) { cur = next; continue; }
-        // pop, skipping subtrees now beyond the hit distance
-        for (;;) {
-            if (sp == 0) {
-                if (rec.prim_idx < 0) rec.t = MAX_DIST;
-                return rec;
-            }
-            --sp;
-            uint64_t e = sp < lds_n ? lds_slot[sp * BVH4_LDS_STRIDE] : stack[sp - lds_n];
-            if (uint_as_float((uint32_t)(e >> 32)) < rec.t) { cur = (int)(uint32_t)e; break; }
-        }
-    }
-}
-
-// While-while variant of the closest-hit walk (Aila & Laine style phase
-// batching, re-derived for wave64): lanes alternate between a node-walk
-// phase and a leaf-test phase at the OUTER loop level, so a wave tends to
-// execute runs of same-kind work instead of interleaving a node step on
-// some lanes with prim tests on others.  Leaf children are POSTPONED onto
-// the stack (tagged entries) instead of intersected inline.  Measured A/B
-// against the inline walk (divergence: VALUUtilization
-// 15% on the inline walk).
-//
-// Stack/cur entry low word: bit31 = leaf, [30:27] = prim count (builders
-// cap leaves at 15 prims), [26:0] = prim base (up to 134M prims).
-HD HitRecord ray_intersect_bvh4_ww(const BVH4Node* nodes,
-                                   const Prim* prims, const uint32_t* prim_obj,
-                                   const Ray& ray, float tmax,
-                                   uint64_t* lds_slot = nullptr, int lds_n = 0,
-                                   const BVH4Node* top_cache = nullptr,
-                                   int n_cached = 0, bool tri_only = false) {
-    HitRecord rec;
-    rec.t = tmax;
-    const Vec3 inv_d = safe_rcp_dir(ray.d);
-    const Vec3 o_div = ray.o * inv_d;
-    uint64_t stack[BVH4_STACK];
-    int sp = 0;
-    constexpr uint32_t DONE = 0x7fffffffu;
     uint32_t cur = 0;
-    for (;;) {
-        // ---- node phase: walk internal nodes until a leaf surfaces
-        while (cur < 0x80000000u && cur != DONE) {
-            // top-of-tree nodes come from the LDS copy (every walk starts at
-            // the root; 95% L2 hit rate means the bound is hit LATENCY, and
-            // LDS is ~4x closer than L2).  Pointer select, single flat load.
-            const BVH4Node* nsrc = (int)cur < n_cached ? top_cache : nodes;
-            const BVH4Node nd = nsrc[cur];
-            uint32_t keys[4];
-            int nhit = 0;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                float t0x = fmaf(nd.lo_x[c], inv_d.x, -o_div.x);
-                float t1x = fmaf(nd.hi_x[c], inv_d.x, -o_div.x);
-                float t0y = fmaf(nd.lo_y[c], inv_d.y, -o_div.y);
-                float t1y = fmaf(nd.hi_y[c], inv_d.y, -o_div.y);
-                float t0z = fmaf(nd.lo_z[c], inv_d.z, -o_div.z);
-                float t1z = fmaf(nd.hi_z[c], inv_d.z, -o_div.z);
-                float enter = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)),
-                                    fmaxf(fminf(t0z, t1z), 0.f));
-                float exit_ = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)),
-                                    fminf(fmaxf(t0z, t1z), rec.t));
-                if (enter <= exit_) keys[nhit++] = (float_as_uint(enter) & ~3u) | (uint32_t)c;
-            }
-            if (nhit > 1) {
-                if (keys[0] > keys[1]) { uint32_t t = keys[0]; keys[0] = keys[1]; keys[1] = t; }
-                if (nhit > 2) {
-                    if (keys[1] > keys[2]) { uint32_t t = keys[1]; keys[1] = keys[2]; keys[2] = t; }
-                    if (keys[0] > keys[1]) { uint32_t t = keys[0]; keys[0] = keys[1]; keys[1] = t; }
-                    if (nhit > 3) {
-                        if (keys[2] > keys[3]) { uint32_t t = keys[2]; keys[2] = keys[3]; keys[3] = t; }
-                        if (keys[1] > keys[2]) { uint32_t t = keys[1]; keys[1] = keys[2]; keys[2] = t; }
-                        if (keys[0] > keys[1]) { uint32_t t = keys[0]; keys[0] = keys[1]; keys[1] = t; }
-                    }
-                }
-            }
-            uint32_t next = DONE;
-            for (int k = nhit - 1; k >= 0; --k) {  // far -> near so near pops first
-                uint32_t lo = bvh4_child_word_at(nd, keys[k] & 3u);
-                if (lo == BVH4_EMPTY_W) continue;  // empty slot
-                if (k == 0) {
-                    next = lo;
-                } else {
-                    uint64_t e = ((uint64_t)(keys[k] & ~3u) << 32) | lo;
-                    if (sp < lds_n) lds_slot[sp * BVH4_LDS_STRIDE] = e;
-                    else stack[sp - lds_n] = e;
-                    ++sp;
-                }
-            }
-            if (next != DONE) { cur = next; continue; }
-            for (;;) {  // pop, culling stale subtrees
-                if (sp == 0) { cur = DONE; break; }
-                --sp;
-                uint64_t e = sp < lds_n ? lds_slot[sp * BVH4_LDS_STRIDE] : stack[sp - lds_n];
-                if (uint_as_float((uint32_t)(e >> 32)) < rec.t) { cur = (uint32_t)e; break; }
+    while (cur != BVH4_NONE_W) {
+        const BVH4Node nd = nodes[cur];
+        BVH_HIT_KEYS(BVH4Node, nd, inv_d, o_div, rec.t, keys, nhit)
+        // internal children: the nearest continues, the rest are pushed
+        cur = BVH4_NONE_W;
+        for (int k = 0; k < nhit; ++k) {
+            const uint32_t w = bvh_child_word_at(nd, keys[k] & 3u);
+            if (w == BVH4_NONE_W) continue;
+            if (bvh4_is_leaf(w)) {
+                bvh4_leaf_hit(prims, prim_obj, ray, bvh4_leaf_base(w), bvh4_leaf_count(w), rec);
+            } else if (cur == BVH4_NONE_W) {
+                cur = w;
+            } else {
+                uint64_t e = ((uint64_t)(keys[k] & ~3u) << 32) | w;
+                BVH_PUSH(stack, sp, lds_slot, lds_n, e)
             }
         }
-        if (cur == DONE) break;
-        // ---- leaf phase: drain consecutive leaf entries
-        while (cur >= 0x80000000u) {
-            bvh4_leaf_hit(prims, prim_obj, ray, (int)(cur & 0x07ffffffu),
-                          (int)((cur >> 27) & 0xfu), rec, tri_only);
-            for (;;) {
-                if (sp == 0) { cur = DONE; break; }
-                --sp;
-                uint64_t e = sp < lds_n ? lds_slot[sp * BVH4_LDS_STRIDE] : stack[sp - lds_n];
-                if (uint_as_float((uint32_t)(e >> 32)) < rec.t) { cur = (uint32_t)e; break; }
-            }
-        }
-        if (cur == DONE) break;
+        if (cur == BVH4_NONE_W) BVH_POP_CLOSER(cur, stack, sp, lds_slot, lds_n, rec.t, break, break)
     }
     if (rec.prim_idx < 0) rec.t = MAX_DIST;
     return rec;
 }
 
-// Any-hit occlusion test: returns true if something blocks [EPSILON, tmax].
-// No ordering (any hit ends the walk) — children are pushed unordered.
+// Any-hit occlusion test with inline leaves: true if something blocks
+// (EPSILON, tmax).  Unordered; only node indices are stacked.  One body for
+// widths 4 and 8.
+template <int W>
+HD bool bvh_any_inline(const BVHWideNode<W>* nodes, const Prim* prims,
+                       const uint32_t* prim_obj, const Ray& ray, float tmax,
+                       uint64_t* lds_slot, int lds_n) {
+    const Vec3 inv_d = safe_rcp_dir(ray.d);
+    const Vec3 o_div = ray.o * inv_d;
+    uint64_t stack[BVH4_STACK];
+    int sp = 0;
+    uint32_t cur = 0;
+    while (cur != BVH4_NONE_W) {
+        const BVHWideNode<W> nd = nodes[cur];
+        cur = BVH4_NONE_W;
+#pragma unroll
+        for (int c = 0; c < W; ++c) {
+            float enter, exit_;
+            bvh_child_slab(nd, c, inv_d, o_div, tmax, enter, exit_);
+            if (enter > exit_) continue;
+            const int ch = nd.child[c];
+            if (ch < 0) {
+                const int base = ~ch, pc = nd.cnt[c];
+                BVH_LEAF_ANY_RETURN(prims, prim_obj, ray, base, pc, tmax)
+            } else if (cur == BVH4_NONE_W) {
+                cur = (uint32_t)ch;
+            } else {
+                BVH_PUSH(stack, sp, lds_slot, lds_n, (uint64_t)(uint32_t)ch)
+            }
+        }
+        if (cur == BVH4_NONE_W) BVH_POP_WORD(cur, stack, sp, lds_slot, lds_n, break)
+    }
+    return false;
+}
 HD bool occlusion_test_bvh4(const BVH4Node* nodes,
                             const Prim* prims, const uint32_t* prim_obj,
                             const Ray& ray, float tmax,
                             uint64_t* lds_slot = nullptr, int lds_n = 0) {
+    return bvh_any_inline(nodes, prims, prim_obj, ray, tmax, lds_slot, lds_n);
+}
+
+// Node-visit / prim-test counting walk for the BVH-cost visualizer
+// (reference pt_impl/bvh_cost.cu:38-101; counts reflect the traversal that
+// actually runs, i.e. the 4-wide tree).  Unordered, inline leaves, boxes
+// culled against the best t so far; the stack is private only.
+HD Vec2 bvh4_cost(const BVH4Node* nodes, const Prim* prims,
+                  const uint32_t* prim_obj, const Ray& ray) {
     const Vec3 inv_d = safe_rcp_dir(ray.d);
     const Vec3 o_div = ray.o * inv_d;
-    int stack[BVH4_STACK];
-    int sp = 0;
-    int cur = 0;
-    while (true) {
-        const BVH4Node nd = nodes[cur];
-        int next = -1;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            float t0x = fmaf(nd.lo_x[c], inv_d.x, -o_div.x);
-            float t1x = fmaf(nd.hi_x[c], inv_d.x, -o_div.x);
-            float t0y = fmaf(nd.lo_y[c], inv_d.y, -o_div.y);
-            float t1y = fmaf(nd.hi_y[c], inv_d.y, -o_div.y);
-            float t0z = fmaf(nd.lo_z[c], inv_d.z, -o_div.z);
-            float t1z = fmaf(nd.hi_z[c], inv_d.z, -o_div.z);
-            float enter = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)),
-                                fmaxf(fminf(t0z, t1z), 0.f));
-            float exit_ = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)),
-                                fminf(fmaxf(t0z, t1z), tmax));
-            if (enter > exit_) continue;
-            int ch = nd.child[c];
-            if (ch < 0) {
-                int base = ~ch, pc = nd.cnt[c];
-                for (int k = 0; k < pc; ++k) {
-                    int pid = base + k;
-                    bool sph = (prim_obj[pid] & PRIM_SPHERE_BIT) != 0;
-                    float u, v;
-                    float t = intersect_prim(prims[pid], sph, ray, u, v);
-                    if (t > EPSILON && t < tmax) return true;
-                }
-            } else if (next < 0) {
-                next = ch;
-            } else {
-                if (sp < lds_n) lds_slot[sp * BVH4_LDS_STRIDE] = (uint64_t)(uint32_t)ch;
-                else stack[sp - lds_n] = ch;
-                ++sp;
-            }
-        }
-        if (next >= 0) { cur = next; continue; }
-        if (sp == 0) return false;
-        --sp;
-        cur = sp < lds_n ? (int)(uint32_t)lds_slot[sp * BVH4_LDS_STRIDE] : stack[sp - lds_n];
-    }
-}
-
-// Phase-batched any-hit occlusion walk: same while-while shaping as the
-// closest-hit walk (leaf children postponed onto the stack so a wave runs
-// node steps and prim tests in separate phases), but unordered and with an
-// immediate `true` return on the first blocking hit.  A/B hook
-// Measured +1-2% against the inline-leaf occlusion walk; now the default.
-HD bool occlusion_test_bvh4_ww(const BVH4Node* nodes,
-                               const Prim* prims, const uint32_t* prim_obj,
-                               const Ray& ray, float tmax,
-                               uint64_t* lds_slot = nullptr, int lds_n = 0,
-                               const BVH4Node* top_cache = nullptr,
-                               int n_cached = 0, bool tri_only = false) {
-    const Vec3 inv_d = safe_rcp_dir(ray.d);
-    const Vec3 o_div = ray.o * inv_d;
-    uint64_t stack[BVH4_STACK];
-    int sp = 0;
-    constexpr uint32_t DONE = 0x7fffffffu;
-    uint32_t cur = 0;
-    for (;;) {
-        while (cur < 0x80000000u && cur != DONE) {
-            const BVH4Node* nsrc = (int)cur < n_cached ? top_cache : nodes;
-            const BVH4Node nd = nsrc[cur];
-            uint32_t next = DONE;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                float t0x = fmaf(nd.lo_x[c], inv_d.x, -o_div.x);
-                float t1x = fmaf(nd.hi_x[c], inv_d.x, -o_div.x);
-                float t0y = fmaf(nd.lo_y[c], inv_d.y, -o_div.y);
-                float t1y = fmaf(nd.hi_y[c], inv_d.y, -o_div.y);
-                float t0z = fmaf(nd.lo_z[c], inv_d.z, -o_div.z);
-                float t1z = fmaf(nd.hi_z[c], inv_d.z, -o_div.z);
-                float enter = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)),
-                                    fmaxf(fminf(t0z, t1z), 0.f));
-                float exit_ = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)),
-                                    fminf(fmaxf(t0z, t1z), tmax));
-                if (enter > exit_) continue;
-                int ch = nd.child[c];
-                int pc = nd.cnt[c];
-                if (ch < 0 && pc == 0) continue;
-                uint32_t lo = ch < 0
-                    ? (0x80000000u | ((uint32_t)pc << 27) | (uint32_t)(~ch))
-                    : (uint32_t)ch;
-                if (next == DONE) {
-                    next = lo;
-                } else {
-                    uint64_t e = (uint64_t)lo;
-                    if (sp < lds_n) lds_slot[sp * BVH4_LDS_STRIDE] = e;
-                    else stack[sp - lds_n] = e;
-                    ++sp;
-                }
-            }
-            if (next != DONE) { cur = next; continue; }
-            if (sp == 0) { cur = DONE; break; }
-            --sp;
-            cur = (uint32_t)(sp < lds_n ? lds_slot[sp * BVH4_LDS_STRIDE]
-                                        : stack[sp - lds_n]);
-        }
-        if (cur == DONE) return false;
-        while (cur >= 0x80000000u) {
-            int base = (int)(cur & 0x07ffffffu);
-            int pc = (int)((cur >> 27) & 0xfu);
-            for (int k = 0; k < pc; ++k) {
-                int pid = base + k;
-                // (skipping this load under tri_only as bvh4_leaf_hit does
-                // was measured: +0.8%, inside the noise bar, not landed)
-                bool sph = (prim_obj[pid] & PRIM_SPHERE_BIT) != 0;
-                float u, v;
-                float t = intersect_prim(prims[pid], sph, ray, u, v);
-                if (t > EPSILON && t < tmax) return true;
-            }
-            if (sp == 0) { cur = DONE; break; }
-            --sp;
-            cur = (uint32_t)(sp < lds_n ? lds_slot[sp * BVH4_LDS_STRIDE]
-                                        : stack[sp - lds_n]);
-        }
-        if (cur == DONE) return false;
-    }
-}
-
-// ----------------------------------------------------------------------
-// Quantized 64-byte 4-wide node (Ylitie-style child-box compression,
-// re-derived for this tree): child AABBs stored as uint8 offsets inside
-// the node's own box, power-of-two per-axis scales so decompression is
-// an fma per bound.  Quantized bounds round OUTWARD (conservative: never
-// misses a hit, a few extra visits).  Halves bytes per dependent node
-// load (1 cacheline, not 2) and doubles LDS top-cache coverage — the
-// walk is latency-bound at 4% VALU, so the extra decompress math is free.
-// Child words are pre-tagged exactly like traversal stack entries:
-// bit31 leaf | [30:27] prim cnt | [26:0] base, or plain node index.
-struct alignas(16) BVH4NodeQ {
-    float ox, oy, oz;        // node box origin
-    uint8_t ex, ey, ez;      // per-axis scale exponents: scale = 2^(e-135)
-    uint8_t pad;
-    uint8_t qlo[4][3];       // child lo offsets (floor)
-    uint8_t qhi[4][3];       // child hi offsets (ceil); qhi<qlo = empty slot
-    uint32_t child[4];       // pre-tagged child words (EMPTY_Q for empty)
-};
-static_assert(sizeof(BVH4NodeQ) == 64, "BVH4NodeQ must be 64 bytes");
-constexpr uint32_t BVH4Q_EMPTY = 0x7fffffffu;
-
-// scale = 2^(e-135): e chosen so extent/255 <= scale (exact for
-// power-of-two extents, <2x conservative otherwise)
-HD float bvh4q_scale(uint8_t e) {
-    return uint_as_float((uint32_t)(e) << 23);  // 2^(e-127)
-}
-
-// Closest-hit while-while walk over the quantized tree.  Same phase
-// batching, ordering and stack discipline as ray_intersect_bvh4_ww; child
-// slab tests run on dequantized bounds.
-HD HitRecord ray_intersect_bvh4q_ww(const BVH4NodeQ* nodes,
-                                    const Prim* prims, const uint32_t* prim_obj,
-                                    const Ray& ray, float tmax,
-                                    uint64_t* lds_slot = nullptr, int lds_n = 0,
-                                    const BVH4NodeQ* top_cache = nullptr,
-                                    int n_cached = 0) {
     HitRecord rec;
-    rec.t = tmax;
-    const Vec3 inv_d = safe_rcp_dir(ray.d);
-    const Vec3 o_div = ray.o * inv_d;
-    uint64_t stack[BVH4_STACK];
+    rec.t = MAX_DIST;
+    int node_visits = 0, prim_tests = 0;
+    uint32_t stack[BVH4_STACK];
+    uint64_t* const no_lds = nullptr;
     int sp = 0;
-    constexpr uint32_t DONE = 0x7fffffffu;
     uint32_t cur = 0;
-    for (;;) {
-        while (cur < 0x80000000u && cur != DONE) {
-            const BVH4NodeQ* nsrc = (int)cur < n_cached ? top_cache : nodes;
-            const BVH4NodeQ nd = nsrc[cur];
-            const float sx = bvh4q_scale(nd.ex), sy = bvh4q_scale(nd.ey), sz = bvh4q_scale(nd.ez);
-            uint32_t keys[4];
-            int nhit = 0;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                if (nd.child[c] == BVH4Q_EMPTY) continue;
-                float lx = fmaf((float)nd.qlo[c][0], sx, nd.ox);
-                float hx = fmaf((float)nd.qhi[c][0], sx, nd.ox);
-                float ly = fmaf((float)nd.qlo[c][1], sy, nd.oy);
-                float hy = fmaf((float)nd.qhi[c][1], sy, nd.oy);
-                float lz = fmaf((float)nd.qlo[c][2], sz, nd.oz);
-                float hz = fmaf((float)nd.qhi[c][2], sz, nd.oz);
-                float t0x = fmaf(lx, inv_d.x, -o_div.x);
-                float t1x = fmaf(hx, inv_d.x, -o_div.x);
-                float t0y = fmaf(ly, inv_d.y, -o_div.y);
-                float t1y = fmaf(hy, inv_d.y, -o_div.y);
-                float t0z = fmaf(lz, inv_d.z, -o_div.z);
-                float t1z = fmaf(hz, inv_d.z, -o_div.z);
-                float enter = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)),
-                                    fmaxf(fminf(t0z, t1z), 0.f));
-                float exit_ = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)),
-                                    fminf(fmaxf(t0z, t1z), rec.t));
-                if (enter <= exit_) keys[nhit++] = (float_as_uint(enter) & ~3u) | (uint32_t)c;
-            }
-            if (nhit > 1) {
-                if (keys[0] > keys[1]) { uint32_t t = keys[0]; keys[0] = keys[1]; keys[1] = t; }
-                if (nhit > 2) {
-                    if (keys[1] > keys[2]) { uint32_t t = keys[1]; keys[1] = keys[2]; keys[2] = t; }
-                    if (keys[0] > keys[1]) { uint32_t t = keys[0]; keys[0] = keys[1]; keys[1] = t; }
-                    if (nhit > 3) {
-                        if (keys[2] > keys[3]) { uint32_t t = keys[2]; keys[2] = keys[3]; keys[3] = t; }
-                        if (keys[1] > keys[2]) { uint32_t t = keys[1]; keys[1] = keys[2]; keys[2] = t; }
-                        if (keys[0] > keys[1]) { uint32_t t = keys[0]; keys[0] = keys[1]; keys[1] = t; }
-                    }
-                }
-            }
-            uint32_t next = DONE;
-            for (int k = nhit - 1; k >= 0; --k) {
-                uint32_t lo = bvh4_sel4(nd.child[0], nd.child[1], nd.child[2],
-                                        nd.child[3], keys[k] & 3u);
-                if (k == 0) {
-                    next = lo;
-                } else {
-                    uint64_t e = ((uint64_t)(keys[k] & ~3u) << 32) | lo;
-                    if (sp < lds_n) lds_slot[sp * BVH4_LDS_STRIDE] = e;
-                    else stack[sp - lds_n] = e;
-                    ++sp;
-                }
-            }
-            if (next != DONE) { cur = next; continue; }
-            for (;;) {
-                if (sp == 0) { cur = DONE; break; }
-                --sp;
-                uint64_t e = sp < lds_n ? lds_slot[sp * BVH4_LDS_STRIDE] : stack[sp - lds_n];
-                if (uint_as_float((uint32_t)(e >> 32)) < rec.t) { cur = (uint32_t)e; break; }
+    while (cur != BVH4_NONE_W) {
+        const BVH4Node nd = nodes[cur];
+        ++node_visits;
+        cur = BVH4_NONE_W;
+        for (int c = 0; c < 4; ++c) {
+            float enter, exit_;
+            bvh_child_slab(nd, c, inv_d, o_div, rec.t, enter, exit_);
+            if (enter > exit_) continue;
+            const int ch = nd.child[c];
+            if (ch < 0) {
+                prim_tests += nd.cnt[c];
+                bvh4_leaf_hit(prims, prim_obj, ray, ~ch, nd.cnt[c], rec);
+            } else if (cur == BVH4_NONE_W) {
+                cur = (uint32_t)ch;
+            } else {
+                BVH_PUSH(stack, sp, no_lds, 0, (uint32_t)ch)
             }
         }
-        if (cur == DONE) break;
-        while (cur >= 0x80000000u) {
-            bvh4_leaf_hit(prims, prim_obj, ray, (int)(cur & 0x07ffffffu),
-                          (int)((cur >> 27) & 0xfu), rec);
-            for (;;) {
-                if (sp == 0) { cur = DONE; break; }
-                --sp;
-                uint64_t e = sp < lds_n ? lds_slot[sp * BVH4_LDS_STRIDE] : stack[sp - lds_n];
-                if (uint_as_float((uint32_t)(e >> 32)) < rec.t) { cur = (uint32_t)e; break; }
-            }
-        }
-        if (cur == DONE) break;
+        if (cur == BVH4_NONE_W) BVH_POP_WORD(cur, stack, sp, no_lds, 0, break)
     }
-    if (rec.prim_idx < 0) rec.t = MAX_DIST;
-    return rec;
+    return {(float)node_visits, (float)prim_tests};
 }
 
-// Any-hit occlusion walk over the quantized tree (unordered, early out).
-HD bool occlusion_test_bvh4q_ww(const BVH4NodeQ* nodes,
-                                const Prim* prims, const uint32_t* prim_obj,
-                                const Ray& ray, float tmax,
-                                uint64_t* lds_slot = nullptr, int lds_n = 0,
-                                const BVH4NodeQ* top_cache = nullptr,
-                                int n_cached = 0) {
-    const Vec3 inv_d = safe_rcp_dir(ray.d);
-    const Vec3 o_div = ray.o * inv_d;
-    uint64_t stack[BVH4_STACK];
-    int sp = 0;
-    constexpr uint32_t DONE = 0x7fffffffu;
-    uint32_t cur = 0;
-    for (;;) {
-        while (cur < 0x80000000u && cur != DONE) {
-            const BVH4NodeQ* nsrc = (int)cur < n_cached ? top_cache : nodes;
-            const BVH4NodeQ nd = nsrc[cur];
-            const float sx = bvh4q_scale(nd.ex), sy = bvh4q_scale(nd.ey), sz = bvh4q_scale(nd.ez);
-            uint32_t next = DONE;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                if (nd.child[c] == BVH4Q_EMPTY) continue;
-                float lx = fmaf((float)nd.qlo[c][0], sx, nd.ox);
-                float hx = fmaf((float)nd.qhi[c][0], sx, nd.ox);
-                float ly = fmaf((float)nd.qlo[c][1], sy, nd.oy);
-                float hy = fmaf((float)nd.qhi[c][1], sy, nd.oy);
-                float lz = fmaf((float)nd.qlo[c][2], sz, nd.oz);
-                float hz = fmaf((float)nd.qhi[c][2], sz, nd.oz);
-                float t0x = fmaf(lx, inv_d.x, -o_div.x);
-                float t1x = fmaf(hx, inv_d.x, -o_div.x);
-                float t0y = fmaf(ly, inv_d.y, -o_div.y);
-                float t1y = fmaf(hy, inv_d.y, -o_div.y);
-                float t0z = fmaf(lz, inv_d.z, -o_div.z);
-                float t1z = fmaf(hz, inv_d.z, -o_div.z);
-                float enter = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)),
-                                    fmaxf(fminf(t0z, t1z), 0.f));
-                float exit_ = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)),
-                                    fminf(fmaxf(t0z, t1z), tmax));
-                if (enter > exit_) continue;
-                uint32_t lo = nd.child[c];
-                if (next == DONE) {
-                    next = lo;
-                } else {
-                    uint64_t e = (uint64_t)lo;
-                    if (sp < lds_n) lds_slot[sp * BVH4_LDS_STRIDE] = e;
-                    else stack[sp - lds_n] = e;
-                    ++sp;
-                }
-            }
-            if (next != DONE) { cur = next; continue; }
-            if (sp == 0) { cur = DONE; break; }
-            --sp;
-            cur = (uint32_t)(sp < lds_n ? lds_slot[sp * BVH4_LDS_STRIDE]
-                                        : stack[sp - lds_n]);
-        }
-        if (cur == DONE) return false;
-        while (cur >= 0x80000000u) {
-            int base = (int)(cur & 0x07ffffffu);
-            int pc = (int)((cur >> 27) & 0xfu);
-            for (int k = 0; k < pc; ++k) {
-                int pid = base + k;
-                bool sph = (prim_obj[pid] & PRIM_SPHERE_BIT) != 0;
-                float u, v;
-                float t = intersect_prim(prims[pid], sph, ray, u, v);
-                if (t > EPSILON && t < tmax) return true;
-            }
-            if (sp == 0) { cur = DONE; break; }
-            --sp;
-            cur = (uint32_t)(sp < lds_n ? lds_slot[sp * BVH4_LDS_STRIDE]
-                                        : stack[sp - lds_n]);
-        }
-        if (cur == DONE) return false;
+// -------------------------------------------------------------- dual walk
+// One thread advances TWO independent closest-hit while-while walks in
+// lockstep steps, so each lane keeps two node loads in flight (the
+// single-ray walk stalls ~58% on L2-hit latency; a second independent chain
+// per lane doubles memory-level parallelism without needing more waves).
+// Used by the wavefront trace kernel (HIPPT_WF_DUAL).  Each walk gets half
+// of the thread's LDS stack slots.
+struct Bvh4Walk {
+    HitRecord rec;
+    uint32_t cur;       // tagged word; BVH4_NONE_W = finished
+    int sp;
+    Vec3 inv_d, o_div;
+    Ray ray;
+    uint64_t stack[BVH4_STACK / 2];
+};
+
+HD void bvh4_walk_init(Bvh4Walk& w, const Ray& ray, float tmax) {
+    w.rec = HitRecord();
+    w.rec.t = tmax;
+    w.cur = 0;
+    w.sp = 0;
+    w.inv_d = safe_rcp_dir(ray.d);
+    w.o_div = ray.o * w.inv_d;
+    w.ray = ray;
+}
+
+// One step: a node visit (test 4 children, descend/push) OR one leaf batch.
+// Returns true while the walk still has work.
+HD bool bvh4_walk_step(Bvh4Walk& w, const BVH4Node* nodes, const Prim* prims,
+                       const uint32_t* prim_obj, uint64_t* lds_slot, int lds_n) {
+    if (w.cur == BVH4_NONE_W) return false;
+    if (bvh4_not_leaf(w.cur)) {
+        const BVH4Node nd = nodes[w.cur];
+        BVH_VISIT_ORDERED(BVH4Node, next, nd, w.inv_d, w.o_div, w.rec.t,
+                          w.stack, w.sp, lds_slot, lds_n)
+        if (next != BVH4_NONE_W) { w.cur = next; return true; }
+    } else {
+        bvh4_leaf_hit(prims, prim_obj, w.ray, bvh4_leaf_base(w.cur),
+                      bvh4_leaf_count(w.cur), w.rec);
     }
+    BVH_POP_CLOSER(w.cur, w.stack, w.sp, lds_slot, lds_n, w.rec.t, return false, return true)
 }
 
 // Host-side conversion fp32 4-wide -> quantized (outward rounding).
@@ -643,7 +645,7 @@ inline std::vector<BVH4NodeQ> quantize_bvh4(const BVH4Node* nodes, int n) {
         const float sxyz[3] = {bvh4q_scale(q.ex), bvh4q_scale(q.ey), bvh4q_scale(q.ez)};
         for (int c = 0; c < 4; ++c) {
             if (s.child[c] == 0 && s.cnt[c] == 0) {
-                q.child[c] = BVH4Q_EMPTY;
+                q.child[c] = BVH4_NONE_W;
                 for (int a = 0; a < 3; ++a) { q.qlo[c][a] = 255; q.qhi[c][a] = 0; }
                 continue;
             }
@@ -656,235 +658,10 @@ inline std::vector<BVH4NodeQ> quantize_bvh4(const BVH4Node* nodes, int n) {
                 q.qlo[c][a] = (uint8_t)clampv((int)fl, 0, 255);
                 q.qhi[c][a] = (uint8_t)clampv((int)fh, 0, 255);
             }
-            q.child[c] = s.child[c] < 0
-                ? (0x80000000u | ((uint32_t)s.cnt[c] << 27) | (uint32_t)(~s.child[c]))
-                : (uint32_t)s.child[c];
+            q.child[c] = bvh4_child_word(s.child[c], s.cnt[c]);
         }
     }
     return out;
-}
-
-// Node-visit / prim-test counting walk for the BVH-cost visualizer
-// (reference pt_impl/bvh_cost.cu:38-101; counts reflect the traversal that
-// actually runs, i.e. the 4-wide one).
-HD Vec2 bvh4_cost(const BVH4Node* nodes, const Prim* prims,
-                  const uint32_t* prim_obj, const Ray& ray) {
-    const Vec3 inv_d = safe_rcp_dir(ray.d);
-    const Vec3 o_div = ray.o * inv_d;
-    float best_t = MAX_DIST;
-    int node_visits = 0, prim_tests = 0;
-    int stack[BVH4_STACK];
-    int sp = 0;
-    int cur = 0;
-    while (true) {
-        const BVH4Node nd = nodes[cur];
-        ++node_visits;
-        int next = -1;
-        for (int c = 0; c < 4; ++c) {
-            float t0x = fmaf(nd.lo_x[c], inv_d.x, -o_div.x);
-            float t1x = fmaf(nd.hi_x[c], inv_d.x, -o_div.x);
-            float t0y = fmaf(nd.lo_y[c], inv_d.y, -o_div.y);
-            float t1y = fmaf(nd.hi_y[c], inv_d.y, -o_div.y);
-            float t0z = fmaf(nd.lo_z[c], inv_d.z, -o_div.z);
-            float t1z = fmaf(nd.hi_z[c], inv_d.z, -o_div.z);
-            float enter = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)),
-                                fmaxf(fminf(t0z, t1z), 0.f));
-            float exit_ = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)),
-                                fminf(fmaxf(t0z, t1z), best_t));
-            if (enter > exit_) continue;
-            int ch = nd.child[c];
-            if (ch < 0) {
-                int base = ~ch, pc = nd.cnt[c];
-                for (int k = 0; k < pc; ++k) {
-                    ++prim_tests;
-                    float u, v;
-                    bool sph = (prim_obj[base + k] & PRIM_SPHERE_BIT) != 0;
-                    float t = intersect_prim(prims[base + k], sph, ray, u, v);
-                    if (t > EPSILON && t < best_t) best_t = t;
-                }
-            } else if (next < 0) {
-                next = ch;
-            } else {
-                stack[sp++] = ch;
-            }
-        }
-        if (next >= 0) { cur = next; continue; }
-        if (sp == 0) return {(float)node_visits, (float)prim_tests};
-        cur = stack[--sp];
-    }
-}
-
-// ----------------------------------------------------------------------
-// Dual-ray while-while walk: one thread advances TWO independent closest-hit
-// walks in lockstep steps, so each lane keeps two node loads in flight (the
-// single-ray walk stalls ~58% on L2-hit latency; a second independent chain
-// per lane doubles memory-level parallelism without needing more waves).
-// Used by the wavefront trace kernel (HIPPT_WF_DUAL).  Each walk gets half
-// of the thread's LDS stack slots.
-struct Bvh4Walk {
-    HitRecord rec;
-    uint32_t cur;       // tagged entry: bit31 leaf, DONE_W = finished
-    int sp;
-    Vec3 inv_d, o_div;
-    Ray ray;
-    uint64_t stack[BVH4_STACK / 2];
-};
-constexpr uint32_t BVH4_DONE_W = 0x7fffffffu;
-
-HD void bvh4_walk_init(Bvh4Walk& w, const Ray& ray, float tmax) {
-    w.rec = HitRecord();
-    w.rec.t = tmax;
-    w.cur = 0;
-    w.sp = 0;
-    w.inv_d = safe_rcp_dir(ray.d);
-    w.o_div = ray.o * w.inv_d;
-    w.ray = ray;
-}
-
-// One step: a node visit (test 4 children, descend/push) OR one leaf batch.
-// Returns true while the walk still has work.
-HD bool bvh4_walk_step(Bvh4Walk& w, const BVH4Node* nodes, const Prim* prims,
-                       const uint32_t* prim_obj, uint64_t* lds_slot, int lds_n) {
-    if (w.cur == BVH4_DONE_W) return false;
-    if (w.cur < 0x80000000u) {
-        const BVH4Node nd = nodes[w.cur];
-        uint32_t keys[4];
-        int nhit = 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            float t0x = fmaf(nd.lo_x[c], w.inv_d.x, -w.o_div.x);
-            float t1x = fmaf(nd.hi_x[c], w.inv_d.x, -w.o_div.x);
-            float t0y = fmaf(nd.lo_y[c], w.inv_d.y, -w.o_div.y);
-            float t1y = fmaf(nd.hi_y[c], w.inv_d.y, -w.o_div.y);
-            float t0z = fmaf(nd.lo_z[c], w.inv_d.z, -w.o_div.z);
-            float t1z = fmaf(nd.hi_z[c], w.inv_d.z, -w.o_div.z);
-            float enter = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)),
-                                fmaxf(fminf(t0z, t1z), 0.f));
-            float exit_ = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)),
-                                fminf(fmaxf(t0z, t1z), w.rec.t));
-            if (enter <= exit_) keys[nhit++] = (float_as_uint(enter) & ~3u) | (uint32_t)c;
-        }
-        if (nhit > 1) {
-            if (keys[0] > keys[1]) { uint32_t t = keys[0]; keys[0] = keys[1]; keys[1] = t; }
-            if (nhit > 2) {
-                if (keys[1] > keys[2]) { uint32_t t = keys[1]; keys[1] = keys[2]; keys[2] = t; }
-                if (keys[0] > keys[1]) { uint32_t t = keys[0]; keys[0] = keys[1]; keys[1] = t; }
-                if (nhit > 3) {
-                    if (keys[2] > keys[3]) { uint32_t t = keys[2]; keys[2] = keys[3]; keys[3] = t; }
-                    if (keys[1] > keys[2]) { uint32_t t = keys[1]; keys[1] = keys[2]; keys[2] = t; }
-                    if (keys[0] > keys[1]) { uint32_t t = keys[0]; keys[0] = keys[1]; keys[1] = t; }
-                }
-            }
-        }
-        uint32_t next = BVH4_DONE_W;
-        for (int k = nhit - 1; k >= 0; --k) {
-            uint32_t lo = bvh4_child_word_at(nd, keys[k] & 3u);
-            if (lo == BVH4_EMPTY_W) continue;
-            if (k == 0) {
-                next = lo;
-            } else {
-                uint64_t e = ((uint64_t)(keys[k] & ~3u) << 32) | lo;
-                if (w.sp < lds_n) lds_slot[w.sp * BVH4_LDS_STRIDE] = e;
-                else w.stack[w.sp - lds_n] = e;
-                ++w.sp;
-            }
-        }
-        if (next != BVH4_DONE_W) { w.cur = next; return true; }
-    } else {
-        bvh4_leaf_hit(prims, prim_obj, w.ray, (int)(w.cur & 0x07ffffffu),
-                      (int)((w.cur >> 27) & 0xfu), w.rec);
-    }
-    // pop (culling stale subtrees)
-    for (;;) {
-        if (w.sp == 0) { w.cur = BVH4_DONE_W; return false; }
-        --w.sp;
-        uint64_t e = w.sp < lds_n ? lds_slot[w.sp * BVH4_LDS_STRIDE] : w.stack[w.sp - lds_n];
-        if (uint_as_float((uint32_t)(e >> 32)) < w.rec.t) { w.cur = (uint32_t)e; return true; }
-    }
-}
-
-// 4-byte-entry variant of the while-while walk: stack entries carry only the
-// tagged node/leaf word (no t_near, so no pop culling).  Halves stack LDS
-// bytes -> twice the LDS entry capacity per thread at the same block budget.
-// Measured 3% SLOWER than the 8-byte culling walk (host-tested record;
-// no device path uses it).  lds_n here counts 4-byte entries.
-HD HitRecord ray_intersect_bvh4_ww32(const BVH4Node* nodes,
-                                     const Prim* prims, const uint32_t* prim_obj,
-                                     const Ray& ray, float tmax,
-                                     uint32_t* lds_slot = nullptr, int lds_n = 0) {
-    HitRecord rec;
-    rec.t = tmax;
-    const Vec3 inv_d = safe_rcp_dir(ray.d);
-    const Vec3 o_div = ray.o * inv_d;
-    uint32_t stack[BVH4_STACK];
-    int sp = 0;
-    constexpr uint32_t DONE = 0x7fffffffu;
-    uint32_t cur = 0;
-    for (;;) {
-        while (cur < 0x80000000u && cur != DONE) {
-            const BVH4Node nd = nodes[cur];
-            uint32_t keys[4];
-            int nhit = 0;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                float t0x = fmaf(nd.lo_x[c], inv_d.x, -o_div.x);
-                float t1x = fmaf(nd.hi_x[c], inv_d.x, -o_div.x);
-                float t0y = fmaf(nd.lo_y[c], inv_d.y, -o_div.y);
-                float t1y = fmaf(nd.hi_y[c], inv_d.y, -o_div.y);
-                float t0z = fmaf(nd.lo_z[c], inv_d.z, -o_div.z);
-                float t1z = fmaf(nd.hi_z[c], inv_d.z, -o_div.z);
-                float enter = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)),
-                                    fmaxf(fminf(t0z, t1z), 0.f));
-                float exit_ = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)),
-                                    fminf(fmaxf(t0z, t1z), rec.t));
-                if (enter <= exit_) keys[nhit++] = (float_as_uint(enter) & ~3u) | (uint32_t)c;
-            }
-            if (nhit > 1) {
-                if (keys[0] > keys[1]) { uint32_t t = keys[0]; keys[0] = keys[1]; keys[1] = t; }
-                if (nhit > 2) {
-                    if (keys[1] > keys[2]) { uint32_t t = keys[1]; keys[1] = keys[2]; keys[2] = t; }
-                    if (keys[0] > keys[1]) { uint32_t t = keys[0]; keys[0] = keys[1]; keys[1] = t; }
-                    if (nhit > 3) {
-                        if (keys[2] > keys[3]) { uint32_t t = keys[2]; keys[2] = keys[3]; keys[3] = t; }
-                        if (keys[1] > keys[2]) { uint32_t t = keys[1]; keys[1] = keys[2]; keys[2] = t; }
-                        if (keys[0] > keys[1]) { uint32_t t = keys[0]; keys[0] = keys[1]; keys[1] = t; }
-                    }
-                }
-            }
-            uint32_t next = DONE;
-            for (int k = nhit - 1; k >= 0; --k) {
-                int c = (int)(keys[k] & 3u);
-                int ch = nd.child[c];
-                int pc = nd.cnt[c];
-                if (ch < 0 && pc == 0) continue;
-                uint32_t lo = ch < 0
-                    ? (0x80000000u | ((uint32_t)pc << 27) | (uint32_t)(~ch))
-                    : (uint32_t)ch;
-                if (k == 0) {
-                    next = lo;
-                } else {
-                    if (sp < lds_n) lds_slot[sp * BVH4_LDS_STRIDE] = lo;
-                    else stack[sp - lds_n] = lo;
-                    ++sp;
-                }
-            }
-            if (next != DONE) { cur = next; continue; }
-            if (sp == 0) { cur = DONE; break; }
-            --sp;
-            cur = sp < lds_n ? lds_slot[sp * BVH4_LDS_STRIDE] : stack[sp - lds_n];
-        }
-        if (cur == DONE) break;
-        while (cur >= 0x80000000u) {
-            bvh4_leaf_hit(prims, prim_obj, ray, (int)(cur & 0x07ffffffu),
-                          (int)((cur >> 27) & 0xfu), rec);
-            if (sp == 0) { cur = DONE; break; }
-            --sp;
-            cur = sp < lds_n ? lds_slot[sp * BVH4_LDS_STRIDE] : stack[sp - lds_n];
-        }
-        if (cur == DONE) break;
-    }
-    if (rec.prim_idx < 0) rec.t = MAX_DIST;
-    return rec;
 }
 
 } // namespace hippt

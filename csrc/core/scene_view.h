@@ -162,8 +162,8 @@ HD const TravNode* trav_nodes(const SceneView& sv) {
 // walk is NOT wired into the kernels — even a dead `if (sv.nodes8)` branch
 // cost ~3% of kernel throughput.  bvh8.h stays host-tested for the record.
 // (A 4-byte-entry stack variant — double LDS capacity, no pop culling —
-// was measured 3% slower: the t_near culling pays for its 8-byte entries.
-// ray_intersect_bvh4_ww32 stays host-tested for the record.)
+// was measured 3% slower: the t_near culling paid for its 8-byte entries.
+// That walk was a host-tested record for a while and has been removed.)
 HD HitRecord scene_intersect(const SceneView& sv, const Ray& ray,
                              float tmax = MAX_DIST, TravCtx tc = {}) {
 #ifdef HIPPT_QBVH

@@ -191,6 +191,27 @@ class TestBVH4:
         o, d = self._rays(500, seed=19)
         assert C.bvh4_selftest(prims, pobj, nodes, nodes4, o, d, 1e7) == 0
 
+    # The kernels keep the bottom lds_n stack entries in LDS and the rest in a
+    # private array; the host passes a strided buffer for the LDS part.  At
+    # lds_n 1 and 3 a walk crosses that boundary in both directions (3 gives
+    # the dual walk's halves one entry each, 1 leaves them private only).
+    @pytest.mark.parametrize("lds_n", [1, 3])
+    @pytest.mark.parametrize("case", ["tiny", "sbvh", "spheres"])
+    def test_traversal_agreement_lds_stack(self, case, lds_n):
+        if case == "tiny":
+            prims, pobj, nodes, nodes4, _ = self._build(2, seed=18)
+            o, d = self._rays(500, seed=19)
+        elif case == "sbvh":
+            prims, pobj, nodes, nodes4, _ = self._build(600, seed=14, use_sbvh=True)
+            o, d = self._rays(4000, seed=15)
+        else:
+            prims, pobj, nodes, nodes4, _ = self._build(400, seed=16, spheres=True)
+            o, d = self._rays(4000, seed=17)
+        nodes8, _ = C.collapse_bvh8(nodes)
+        assert C.bvh4_selftest(prims, pobj, nodes, nodes4, o, d, 1e7, nodes8,
+                               lds_n=lds_n) == 0
+        assert C.bvh4q_selftest(prims, pobj, nodes4, o, d, 1e7, lds_n=lds_n) == 0
+
     def test_bvh8_agreement(self):
         prims, pobj, nodes, nodes4, _ = self._build(800, seed=21)
         nodes8, depth8 = C.collapse_bvh8(nodes)
