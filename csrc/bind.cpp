@@ -87,6 +87,8 @@ int bvh4_tree_depth(const BVH4Node* nodes, int n) {
     return maxd;
 }
 
+static std::vector<uint64_t> host_lds_slots(int lds_n);   // below, with the self-tests
+
 struct SceneHolder {
     // ----- host data (kept alive / owned)
     farr np_prims, np_attrs, np_nodes, np_nodes4, np_nodes8;
@@ -157,6 +159,9 @@ struct SceneHolder {
         nodes4q = np_nodes4.ndim() == 2 && np_nodes4.shape(0) > 0
             ? quantize_bvh4((const BVH4Node*)np_nodes4.data(), (int)np_nodes4.shape(0))
             : std::vector<BVH4NodeQ>();
+        nodes4t = np_nodes4.ndim() == 2 && np_nodes4.shape(0) > 0
+            ? tag_bvh4((const BVH4Node*)np_nodes4.data(), (int)np_nodes4.shape(0))
+            : std::vector<BVH4NodeT>();
         // scene bounding sphere (envmap sample_le disk origin)
         const Prim* pr = (const Prim*)np_prims.data();
         const uint32_t* po = np_prim_obj.data();
@@ -187,6 +192,7 @@ struct SceneHolder {
     int cache_nodes = 0;
     int tri_only = 0;
     std::vector<BVH4NodeQ> nodes4q;   // quantized mirror of np_nodes4
+    std::vector<BVH4NodeT> nodes4t;   // traversal mirror: pre-tagged child words
 
     void set_cache_level(int level) {
         // accelerator XML cache_level -> top-tree nodes in LDS (2^level,
@@ -575,6 +581,7 @@ struct SceneHolder {
         host_sv.nodes = (const BVHNode*)np_nodes.data();
         host_sv.nodes4 = host_sv.n_nodes4 > 0 ? (const BVH4Node*)np_nodes4.data() : nullptr;
         host_sv.nodes4q = nodes4q.empty() ? nullptr : nodes4q.data();
+        host_sv.nodes4t = nodes4t.empty() ? nullptr : nodes4t.data();
         host_sv.nodes8 = host_sv.n_nodes8 > 0 ? (const BVH8Node*)np_nodes8.data() : nullptr;
         host_sv.prims = (const Prim*)np_prims.data();
         host_sv.attrs = (const PrimAttr*)np_attrs.data();
@@ -613,6 +620,8 @@ struct SceneHolder {
             ? upload_vec((const BVH4Node*)np_nodes4.data(), np_nodes4.shape(0)) : nullptr;
         dev_sv.nodes4q = nodes4q.empty() ? nullptr
             : upload_vec(nodes4q.data(), nodes4q.size());
+        dev_sv.nodes4t = nodes4t.empty() ? nullptr
+            : upload_vec(nodes4t.data(), nodes4t.size());
         dev_sv.nodes8 = dev_sv.n_nodes8 > 0
             ? upload_vec((const BVH8Node*)np_nodes8.data(), np_nodes8.shape(0)) : nullptr;
         dev_sv.prims = upload_vec((const Prim*)np_prims.data(), np_prims.shape(0));
@@ -735,16 +744,22 @@ struct SceneHolder {
         if (device < 0) {
             finalize();
             if (host_sv.n_nodes4 <= 0) throw std::runtime_error("trace_rays: empty scene");
+            // lds_n > 0: the bottom lds_n stack entries go to a strided host
+            // buffer, as the kernels keep them in LDS (no top-tree cache here)
+            std::vector<uint64_t> slots = host_lds_slots(lds_n > 0 ? lds_n : 0);
+            TravCtx tc;
+            if (lds_n > 0) { tc.lds_slot = bvh_host_slot(slots.data()); tc.lds_n = lds_n; }
+            plan[0] = tc.lds_n;
             for (int i = 0; i < n; ++i) {
                 Ray r;
                 r.o = {o.at(i, 0), o.at(i, 1), o.at(i, 2)};
                 r.d = {d.at(i, 0), d.at(i, 1), d.at(i, 2)};
-                HitRecord h = scene_intersect(host_sv, r, tmax.at(i));
+                HitRecord h = scene_intersect(host_sv, r, tmax.at(i), tc);
                 t_out.mutable_at(i) = h.t;
                 u_out.mutable_at(i) = h.u;
                 v_out.mutable_at(i) = h.v;
                 p_out.mutable_at(i) = h.prim_idx;
-                occ_out.mutable_at(i) = scene_occluded(host_sv, r, tmax.at(i)) ? 1 : 0;
+                occ_out.mutable_at(i) = scene_occluded(host_sv, r, tmax.at(i), tc) ? 1 : 0;
             }
         } else {
             if (!has_dev) throw std::runtime_error("scene not uploaded to device");
@@ -872,13 +887,16 @@ int py_bvh4_selftest(farr prims, uarr prim_obj, farr nodes, farr nodes4,
     int n_nodes = (int)nodes.shape(0);
     const BVHNode* bn = (const BVHNode*)nodes.data();
     const BVH4Node* n4 = (const BVH4Node*)nodes4.data();
+    // what the device walks load (the ww and dual walks run on it)
+    const std::vector<BVH4NodeT> t4v = tag_bvh4(n4, (int)nodes4.shape(0));
+    const BVH4NodeT* t4 = t4v.data();
     const Prim* pr = (const Prim*)prims.data();
     const uint32_t* po = prim_obj.data();
     std::vector<uint64_t> slots = host_lds_slots(lds_n);
-    uint64_t* lds = lds_n ? slots.data() : nullptr;
+    LdsSlot lds = bvh_host_slot(lds_n ? slots.data() : nullptr);
     // the dual walk halves the slots the way k_wf_trace_dual does
     const int lds_half = lds_n / 2;
-    uint64_t* lds1 = lds_n ? lds + (size_t)lds_half * BVH4_LDS_STRIDE : nullptr;
+    LdsSlot lds1 = lds_n ? lds + (size_t)lds_half * BVH4_LDS_STRIDE : nullptr;
     int bad = 0;
     int nr = (int)ray_o.shape(0);
     for (int i = 0; i < nr; ++i) {
@@ -887,7 +905,7 @@ int py_bvh4_selftest(farr prims, uarr prim_obj, farr nodes, farr nodes4,
         r.d = {ray_d.at(i, 0), ray_d.at(i, 1), ray_d.at(i, 2)};
         HitRecord a = ray_intersect_bvh(bn, n_nodes, pr, po, r, tmax);
         HitRecord b = ray_intersect_bvh4(n4, pr, po, r, tmax, lds, lds_n);
-        HitRecord w = ray_intersect_bvh4_ww(n4, pr, po, r, tmax, lds, lds_n);
+        HitRecord w = ray_intersect_bvh4_ww(t4, pr, po, r, tmax, lds, lds_n);
         if (!same_hit(b, w)) { ++bad; continue; }
         {
             // two walks of the same ray in lockstep, each on its half
@@ -896,8 +914,8 @@ int py_bvh4_selftest(farr prims, uarr prim_obj, farr nodes, farr nodes4,
             bvh4_walk_init(wk1, r, tmax);
             bool r0 = true, r1 = true;
             while (r0 || r1) {
-                if (r0) r0 = bvh4_walk_step(wk0, n4, pr, po, lds, lds_half);
-                if (r1) r1 = bvh4_walk_step(wk1, n4, pr, po, lds1, lds_half);
+                if (r0) r0 = bvh4_walk_step(wk0, t4, pr, po, lds, lds_half);
+                if (r1) r1 = bvh4_walk_step(wk1, t4, pr, po, lds1, lds_half);
             }
             if (wk0.rec.prim_idx < 0) wk0.rec.t = MAX_DIST;
             if (wk1.rec.prim_idx < 0) wk1.rec.t = MAX_DIST;
@@ -911,7 +929,7 @@ int py_bvh4_selftest(farr prims, uarr prim_obj, farr nodes, farr nodes4,
         }
         bool occ_a = occlusion_test_bvh(bn, n_nodes, pr, po, r, tmax);
         bool occ_b = occlusion_test_bvh4(n4, pr, po, r, tmax, lds, lds_n);
-        if (occlusion_test_bvh4_ww(n4, pr, po, r, tmax, lds, lds_n) != occ_b) { ++bad; continue; }
+        if (occlusion_test_bvh4_ww(t4, pr, po, r, tmax, lds, lds_n) != occ_b) { ++bad; continue; }
         if (!same_hit(a, b) || occ_a != occ_b) ++bad;
     }
     return bad;
@@ -926,22 +944,72 @@ int py_bvh4q_selftest(farr prims, uarr prim_obj, farr nodes4,
     const BVH4Node* n4 = (const BVH4Node*)nodes4.data();
     int nn = (int)nodes4.shape(0);
     std::vector<BVH4NodeQ> q = quantize_bvh4(n4, nn);
+    const std::vector<BVH4NodeT> t4v = tag_bvh4(n4, nn);
+    const BVH4NodeT* t4 = t4v.data();
     const Prim* pr = (const Prim*)prims.data();
     const uint32_t* po = prim_obj.data();
     std::vector<uint64_t> slots = host_lds_slots(lds_n);
-    uint64_t* lds = lds_n ? slots.data() : nullptr;
+    LdsSlot lds = bvh_host_slot(lds_n ? slots.data() : nullptr);
     int bad = 0;
     int nr = (int)ray_o.shape(0);
     for (int i = 0; i < nr; ++i) {
         Ray r;
         r.o = {ray_o.at(i, 0), ray_o.at(i, 1), ray_o.at(i, 2)};
         r.d = {ray_d.at(i, 0), ray_d.at(i, 1), ray_d.at(i, 2)};
-        HitRecord a = ray_intersect_bvh4_ww(n4, pr, po, r, tmax, lds, lds_n);
+        HitRecord a = ray_intersect_bvh4_ww(t4, pr, po, r, tmax, lds, lds_n);
         HitRecord b = ray_intersect_bvh4q_ww(q.data(), pr, po, r, tmax, lds, lds_n);
         if (!same_hit(a, b)) { ++bad; continue; }
-        bool oa = occlusion_test_bvh4_ww(n4, pr, po, r, tmax, lds, lds_n);
+        bool oa = occlusion_test_bvh4_ww(t4, pr, po, r, tmax, lds, lds_n);
         bool ob = occlusion_test_bvh4q_ww(q.data(), pr, po, r, tmax, lds, lds_n);
         if (oa != ob) ++bad;
+    }
+    return bad;
+}
+
+// The traversal mirror of a (m,32) BVH4 array as (m,32) uint32: 24 box
+// words, the 4 tagged child words, 4 words of padding.
+uarr py_bvh4_tag(farr nodes4) {
+    if (nodes4.ndim() != 2 || nodes4.shape(1) != 32) throw std::runtime_error("nodes4 must be (m,32)");
+    const std::vector<BVH4NodeT> t4 =
+        tag_bvh4((const BVH4Node*)nodes4.data(), (int)nodes4.shape(0));
+    uarr out({(py::ssize_t)t4.size(), (py::ssize_t)32});
+    std::memcpy(out.mutable_data(), t4.data(), t4.size() * sizeof(BVH4NodeT));
+    return out;
+}
+
+// Node-visit self-test: for every (ray, node) pair one ordered visit the
+// BVH4Node way (run-time key count, network in nested ifs, push loop,
+// per-child tagging) and one the tagged-node way (BVH_VISIT_TAGGED4), each on
+// an empty private stack, culling against tmax.  `next` and every pushed
+// 64-bit entry must be equal.  Returns the number of mismatching pairs.
+int py_bvh4_visit_selftest(farr nodes4, farr ray_o, farr ray_d, float tmax) {
+    if (nodes4.ndim() != 2 || nodes4.shape(1) != 32) throw std::runtime_error("nodes4 must be (m,32)");
+    const BVH4Node* n4 = (const BVH4Node*)nodes4.data();
+    const int nn = (int)nodes4.shape(0);
+    const std::vector<BVH4NodeT> t4 = tag_bvh4(n4, nn);
+    const LdsSlot no_lds = nullptr;
+    int bad = 0;
+    const int nr = (int)ray_o.shape(0);
+    for (int i = 0; i < nr; ++i) {
+        Ray r;
+        r.o = {ray_o.at(i, 0), ray_o.at(i, 1), ray_o.at(i, 2)};
+        r.d = {ray_d.at(i, 0), ray_d.at(i, 1), ray_d.at(i, 2)};
+        const Vec3 inv_d = safe_rcp_dir(r.d);
+        const Vec3 o_div = r.o * inv_d;
+        for (int j = 0; j < nn; ++j) {
+            uint64_t sa[4] = {0, 0, 0, 0}, sb[4] = {0, 0, 0, 0};
+            int spa = 0, spb = 0;
+            uint32_t na, nb;
+            {
+                const BVH4Node nd = n4[j];
+                BVH_VISIT_ORDERED(BVH4Node, na, nd, inv_d, o_div, tmax, sa, spa, no_lds, 0)
+            }
+            {
+                const BVH4NodeT nd = t4[j];
+                BVH_VISIT_TAGGED4(nb, nd, inv_d, o_div, tmax, sb, spb, no_lds, 0)
+            }
+            if (na != nb || spa != spb || std::memcmp(sa, sb, sizeof(sa)) != 0) ++bad;
+        }
     }
     return bad;
 }
@@ -949,7 +1017,9 @@ int py_bvh4q_selftest(farr prims, uarr prim_obj, farr nodes4,
 // Closest-hit query over the BVH4 tree: returns (t, prim) arrays for rays.
 py::tuple py_bvh4_hit(farr prims, uarr prim_obj, farr nodes4,
                       farr ray_o, farr ray_d) {
-    const BVH4Node* n4 = (const BVH4Node*)nodes4.data();
+    const std::vector<BVH4NodeT> t4v =
+        tag_bvh4((const BVH4Node*)nodes4.data(), (int)nodes4.shape(0));
+    const BVH4NodeT* n4 = t4v.data();
     const Prim* pr = (const Prim*)prims.data();
     const uint32_t* po = prim_obj.data();
     int nr = (int)ray_o.shape(0);
@@ -1088,6 +1158,9 @@ PYBIND11_MODULE(_C, m) {
     m.def("collapse_bvh4", &py_collapse_bvh4, py::arg("nodes"));
     m.def("collapse_bvh8", &py_collapse_bvh8, py::arg("nodes"));
     m.def("bvh4_hit", &py_bvh4_hit);
+    m.def("bvh4_tag", &py_bvh4_tag, py::arg("nodes4"));
+    m.def("bvh4_visit_selftest", &py_bvh4_visit_selftest, py::arg("nodes4"),
+          py::arg("ray_o"), py::arg("ray_d"), py::arg("tmax"));
     m.def("bsdf_check", &py_bsdf_check);
     m.def("env_check", &py_env_check);
     m.def("bvh4q_selftest", &py_bvh4q_selftest,

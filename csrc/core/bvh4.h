@@ -8,7 +8,8 @@
 // latency-bound on L2/HBM, profiles/README.md), so the fix is to shorten the
 // chain, not to widen the fetch of a single step (speculative dual-fetch was
 // measured -18%).  A 4-wide node:
-//   * is one 128-byte record = 8 independent 16-byte loads per step — the
+//   * is one 128-byte record = 7 independent 16-byte loads per step (the
+//     traversal node BVH4NodeT: boxes + pre-tagged child words) — the
 //     memory parallelism lives INSIDE one step of the dependent chain,
 //   * halves tree depth (half as many dependent steps per ray),
 //   * tests 4 AABBs per step with pure VALU work, which is nearly free at 4%
@@ -35,6 +36,12 @@
 // bvh-cost visualiser is instruction for instruction what the hand-copied
 // walks compiled to (profiles/README.md).
 //
+// Since the node copy stays in registers the walk is bound by instruction
+// issue, not by latency (VALUBusy 71% at ~13 of 64 lanes active), so the
+// device walks run on BVH4NodeT and visit it with BVH_VISIT_TAGGED4, the
+// branch-free width-4 form of the ordered visit; the BVH4Node forms stay for
+// the host walks, width 8 and as the other side of C.bvh4_visit_selftest.
+//
 // Which walks a kernel can reach in the default build:
 //   ray_intersect_bvh4_ww, occlusion_test_bvh4_ww   every render kernel
 //   bvh4_walk_step                                  k_wf_trace_dual
@@ -53,13 +60,15 @@ namespace hippt {
 // cache lines.
 //   child[c] >= 0 : internal child, index of a node
 //   child[c] <  0 : leaf child, prim_base = ~child[c], prim count = cnt[c]
-//   cnt[c] == 0 AND child[c] == 0: empty slot (box is inverted: never hits)
+//   child[c] <  0 AND cnt[c] == 0: empty slot (collapse_bvh4 writes ~0 and a
+//                   far-away point box, so it is almost never hit either)
 // The walks apply the empty-slot rule (a leaf child of no prims is dropped)
 // after the slab test, so it is paid only for children whose box is hit.
 template <int W>
 struct alignas(16) BVHWideNode {
     static constexpr int WIDTH = W;
     static constexpr bool EMPTY_BEFORE_BOX = false;
+    static constexpr bool TAGGED = false;
     float lo_x[W], lo_y[W], lo_z[W];
     float hi_x[W], hi_y[W], hi_z[W];
     int32_t child[W];
@@ -67,6 +76,25 @@ struct alignas(16) BVHWideNode {
 };
 using BVH4Node = BVHWideNode<4>;
 static_assert(sizeof(BVH4Node) == 128, "BVH4Node must be 128 bytes");
+
+// Traversal node: the BVH4Node the device walks load.  Same boxes; in place
+// of child[] it stores the tagged word of every slot (bvh4_child_word below:
+// BVH4_NONE_W for an empty slot or a leaf of no prims), so a visit neither
+// loads cnt[] nor builds words — 7 x 16-byte loads instead of 8.  The last
+// 16 bytes are padding no walk loads: the record stays 128 bytes so that no
+// node straddles a cache line.  Made once per scene from the BVH4Node array
+// (tag_bvh4 at the end of this file); builders, the scene cache and the
+// inline host walks stay on BVH4Node.
+struct alignas(16) BVH4NodeT {
+    static constexpr int WIDTH = 4;
+    static constexpr bool EMPTY_BEFORE_BOX = false;
+    static constexpr bool TAGGED = true;
+    float lo_x[4], lo_y[4], lo_z[4];
+    float hi_x[4], hi_y[4], hi_z[4];
+    uint32_t child[4];       // tagged child words
+    uint32_t pad[4];
+};
+static_assert(sizeof(BVH4NodeT) == 128, "BVH4NodeT must be 128 bytes");
 
 // Quantized 64-byte 4-wide node (Ylitie-style child-box compression,
 // re-derived for this tree): child AABBs stored as uint8 offsets inside
@@ -78,7 +106,8 @@ static_assert(sizeof(BVH4Node) == 128, "BVH4Node must be 128 bytes");
 struct alignas(16) BVH4NodeQ {
     static constexpr int WIDTH = 4;
     static constexpr bool EMPTY_BEFORE_BOX = true;
-    float ox, oy, oz;        // node box origin
+    static constexpr bool TAGGED = true;
+    float ox, oy, oz;       // node box origin
     uint8_t ex, ey, ez;      // per-axis scale exponents: scale = 2^(e-127)
     uint8_t pad;
     uint8_t qlo[4][3];       // child lo offsets (floor)
@@ -135,12 +164,16 @@ HD uint32_t bvh_child_word_at(const BVH4Node& nd, uint32_t slot) {
 HD uint32_t bvh_child_word_at(const BVH4NodeQ& nd, uint32_t slot) {
     return bvh4_sel4(nd.child[0], nd.child[1], nd.child[2], nd.child[3], slot);
 }
+HD uint32_t bvh_child_word_at(const BVH4NodeT& nd, uint32_t slot) {
+    return bvh4_sel4(nd.child[0], nd.child[1], nd.child[2], nd.child[3], slot);
+}
 // Word of child c (a constant) of a slot already known not to be empty.
 template <int W>
 HD uint32_t bvh_filled_child_word(const BVHWideNode<W>& nd, int c) {
     return bvh4_filled_word(nd.child[c], nd.cnt[c]);
 }
 HD uint32_t bvh_filled_child_word(const BVH4NodeQ& nd, int c) { return nd.child[c]; }
+HD uint32_t bvh_filled_child_word(const BVH4NodeT& nd, int c) { return nd.child[c]; }
 
 // -------------------------------------------------------------- slab test
 // Box [lo, hi] against the ray (inv_d, o_div = o * inv_d) on [0, tmax]: the
@@ -167,6 +200,12 @@ template <int W>
 HD bool bvh_slot_known_empty(const BVHWideNode<W>&, int) { return false; }
 template <int W>
 HD void bvh_child_slab(const BVHWideNode<W>& nd, int c, const Vec3& inv_d,
+                       const Vec3& o_div, float tmax, float& enter, float& exit_) {
+    bvh_slab(nd.lo_x[c], nd.lo_y[c], nd.lo_z[c], nd.hi_x[c], nd.hi_y[c], nd.hi_z[c],
+             inv_d, o_div, tmax, enter, exit_);
+}
+HD bool bvh_slot_known_empty(const BVH4NodeT&, int) { return false; }
+HD void bvh_child_slab(const BVH4NodeT& nd, int c, const Vec3& inv_d,
                        const Vec3& o_div, float tmax, float& enter, float& exit_) {
     bvh_slab(nd.lo_x[c], nd.lo_y[c], nd.lo_z[c], nd.hi_x[c], nd.hi_y[c], nd.hi_z[c],
              inv_d, o_div, tmax, enter, exit_);
@@ -243,6 +282,20 @@ HD void bvh_child_slab(const BVH4NodeQ& nd, int c, const Vec3& inv_d,
 // entries whose t_near is already beyond the current hit are skipped without
 // a node load; unordered walks store the bare word.
 constexpr int BVH4_LDS_STRIDE = 256;  // all render blocks are 256 threads
+// The per-thread slot pointer.  Under device compilation it is an
+// address-space-3 pointer: through a generic pointer a pop is a flat load
+// behind a run-time choice between the shared and the private aperture and a
+// wait on both counters; typed, the LDS half of push and pop is a plain
+// ds_write_b64 / ds_read_b64.  Kernels cast their __shared__ address once,
+// where they fill in TravCtx.  On the host it is a plain pointer.
+#if HIPPT_ON_DEVICE
+using LdsSlot = __attribute__((address_space(3))) uint64_t*;
+#else
+using LdsSlot = uint64_t*;
+#endif
+// A host buffer standing in for a thread's LDS slots (the self-tests of
+// bind.cpp; the cast exists for the device pass over that host code).
+HD LdsSlot bvh_host_slot(uint64_t* p) { return (LdsSlot)p; }
 
 #define BVH_PUSH(stack, sp, lds_slot, lds_n, e)                       \
     {                                                                 \
@@ -270,9 +323,10 @@ constexpr int BVH4_LDS_STRIDE = 256;  // all render blocks are 256 threads
 
 // Ordered visit of node nd: push the hit children far -> near (so the near
 // ones pop first); next = the nearest one's word, BVH4_NONE_W if none is hit.
+// (`next` is the caller's variable.)
 #define BVH_VISIT_ORDERED(Node, next, nd, inv_d, o_div, tmax, stack, sp, lds_slot, lds_n) \
     BVH_HIT_KEYS(Node, nd, inv_d, o_div, tmax, keys_, nhit_)                           \
-    uint32_t next = BVH4_NONE_W;                                                       \
+    next = BVH4_NONE_W;                                                                \
     for (int k_ = nhit_ - 1; k_ >= 0; --k_) {                                          \
         uint32_t lo_ = bvh_child_word_at(nd, keys_[k_] & (Node::WIDTH - 1u));          \
         if (lo_ == BVH4_NONE_W) continue; /* empty slot */                             \
@@ -282,6 +336,68 @@ constexpr int BVH4_LDS_STRIDE = 256;  // all render blocks are 256 threads
             uint64_t e_ = ((uint64_t)(keys_[k_] & ~(Node::WIDTH - 1u)) << 32) | lo_;   \
             BVH_PUSH(stack, sp, lds_slot, lds_n, e_)                                   \
         }                                                                              \
+    }
+
+// The same visit for a width-4 node of tagged words (BVH4NodeT, BVH4NodeQ),
+// without a run-time count or index: the device form.  Under wave64
+// divergence every instruction of the visit costs a full issue slot however
+// few lanes need it, so the form above is dear there: `keys[nhit++]` on a
+// run-time nhit is a compare/select cascade per child, the sort sits in
+// nested exec-masked blocks that a divergent wave enters nearly all of, and
+// the push loop runs max(nhit) times per wave with a select tree per pass.
+// Here a missed child gets the key BVH4_MISS_KEY, above every hit key (a
+// hit key's top bit is clear: t_near >= 0), all four keys go through a fixed
+// 5-comparator min/max network, and the three far keys are pushed far ->
+// near in unrolled steps.  Hit keys are distinct (the slot is in the low
+// bits), so any correct sort gives the order of the form above: `next` and
+// every pushed entry are the same (tests/test_visit_host.py compares them).
+constexpr uint32_t BVH4_MISS_KEY = 0xffffffffu;
+#define BVH_KEY_MINMAX(a, b)                                              \
+    {                                                                     \
+        const uint32_t lo_ = (a) < (b) ? (a) : (b);                       \
+        const uint32_t hi_ = (a) < (b) ? (b) : (a);                       \
+        (a) = lo_; (b) = hi_;                                             \
+    }
+#define BVH_KEY4(key, nd, c, inv_d, o_div, tmax)                          \
+    uint32_t key;                                                         \
+    {                                                                     \
+        float enter_, exit_;                                              \
+        bvh_child_slab(nd, c, inv_d, o_div, tmax, enter_, exit_);         \
+        key = !bvh_slot_known_empty(nd, c) && enter_ <= exit_             \
+            ? (float_as_uint(enter_) & ~3u) | (uint32_t)(c) : BVH4_MISS_KEY; \
+    }
+// Tagged word behind a sorted key: BVH4_NONE_W for a miss (and for a hit
+// leaf of no prims, which the word already says).
+#define BVH_KEY4_WORD(nd, key) \
+    ((key) == BVH4_MISS_KEY ? BVH4_NONE_W : bvh_child_word_at(nd, (key) & 3u))
+#define BVH_PUSH_KEY4(nd, key, stack, sp, lds_slot, lds_n)                \
+    {                                                                     \
+        const uint32_t w_ = BVH_KEY4_WORD(nd, key);                       \
+        if (w_ != BVH4_NONE_W) {                                          \
+            uint64_t e_ = ((uint64_t)((key) & ~3u) << 32) | w_;           \
+            BVH_PUSH(stack, sp, lds_slot, lds_n, e_)                      \
+        }                                                                 \
+    }
+#define BVH_VISIT_TAGGED4(next, nd, inv_d, o_div, tmax, stack, sp, lds_slot, lds_n) \
+    BVH_KEY4(k0_, nd, 0, inv_d, o_div, tmax)                              \
+    BVH_KEY4(k1_, nd, 1, inv_d, o_div, tmax)                              \
+    BVH_KEY4(k2_, nd, 2, inv_d, o_div, tmax)                              \
+    BVH_KEY4(k3_, nd, 3, inv_d, o_div, tmax)                              \
+    BVH_KEY_MINMAX(k0_, k1_)                                              \
+    BVH_KEY_MINMAX(k2_, k3_)                                              \
+    BVH_KEY_MINMAX(k0_, k2_)                                              \
+    BVH_KEY_MINMAX(k1_, k3_)                                              \
+    BVH_KEY_MINMAX(k1_, k2_)                                              \
+    BVH_PUSH_KEY4(nd, k3_, stack, sp, lds_slot, lds_n)                    \
+    BVH_PUSH_KEY4(nd, k2_, stack, sp, lds_slot, lds_n)                    \
+    BVH_PUSH_KEY4(nd, k1_, stack, sp, lds_slot, lds_n)                    \
+    next = BVH_KEY4_WORD(nd, k0_);
+// The visit a walk over `Node` runs.
+#define BVH_VISIT(Node, next, nd, inv_d, o_div, tmax, stack, sp, lds_slot, lds_n)      \
+    if constexpr (Node::WIDTH == 4 && Node::TAGGED) {                                  \
+        BVH_VISIT_TAGGED4(next, nd, inv_d, o_div, tmax, stack, sp, lds_slot, lds_n)    \
+    } else {                                                                           \
+        BVH_VISIT_ORDERED(Node, next, nd, inv_d, o_div, tmax, stack, sp, lds_slot, lds_n) \
     }
 
 // ------------------------------------------------------------- leaf loops
@@ -304,12 +420,11 @@ HD void bvh4_leaf_hit(const Prim* prims, const uint32_t* prim_obj,
 }
 // Any-hit form: `return true` from the walk if a prim of [base, base+cnt)
 // blocks (EPSILON, tmax).  A macro because it leaves the walk from inside
-// the loop.  (Skipping the prim_obj load under tri_only as bvh4_leaf_hit
-// does was measured: +0.8%, inside the noise bar, not landed.)
-#define BVH_LEAF_ANY_RETURN(prims, prim_obj, ray, base, cnt, tmax)            \
+// the loop.  tri_only as in bvh4_leaf_hit.
+#define BVH_LEAF_ANY_RETURN(prims, prim_obj, ray, base, cnt, tmax, tri_only)  \
     for (int k_ = 0; k_ < (cnt); ++k_) {                                      \
         int pid_ = (base) + k_;                                               \
-        bool sph_ = ((prim_obj)[pid_] & PRIM_SPHERE_BIT) != 0;                \
+        bool sph_ = !(tri_only) && ((prim_obj)[pid_] & PRIM_SPHERE_BIT) != 0; \
         float u_, v_;                                                         \
         float t_ = intersect_prim((prims)[pid_], sph_, ray, u_, v_);          \
         if (t_ > EPSILON && t_ < (tmax)) return true;                         \
@@ -326,7 +441,7 @@ HD void bvh4_leaf_hit(const Prim* prims, const uint32_t* prim_obj,
 template <class Node>
 HD HitRecord bvh_closest_ww(const Node* nodes, const Prim* prims,
                             const uint32_t* prim_obj, const Ray& ray, float tmax,
-                            uint64_t* lds_slot, int lds_n, const Node* top_cache,
+                            LdsSlot lds_slot, int lds_n, const Node* top_cache,
                             int n_cached, bool tri_only) {
     HitRecord rec;
     rec.t = tmax;
@@ -343,8 +458,8 @@ HD HitRecord bvh_closest_ww(const Node* nodes, const Prim* prims,
             // LDS is ~4x closer than L2).  Pointer select, single flat load.
             const Node* nsrc = (int)cur < n_cached ? top_cache : nodes;
             const Node nd = nsrc[cur];
-            BVH_VISIT_ORDERED(Node, next, nd, inv_d, o_div, rec.t,
-                              stack, sp, lds_slot, lds_n)
+            uint32_t next;
+            BVH_VISIT(Node, next, nd, inv_d, o_div, rec.t, stack, sp, lds_slot, lds_n)
             if (next != BVH4_NONE_W) { cur = next; continue; }
             BVH_POP_CLOSER(cur, stack, sp, lds_slot, lds_n, rec.t, break, break)
         }
@@ -366,8 +481,8 @@ HD HitRecord bvh_closest_ww(const Node* nodes, const Prim* prims,
 // the default.
 template <class Node>
 HD bool bvh_any_ww(const Node* nodes, const Prim* prims, const uint32_t* prim_obj,
-                   const Ray& ray, float tmax, uint64_t* lds_slot, int lds_n,
-                   const Node* top_cache, int n_cached) {
+                   const Ray& ray, float tmax, LdsSlot lds_slot, int lds_n,
+                   const Node* top_cache, int n_cached, bool tri_only) {
     const Vec3 inv_d = safe_rcp_dir(ray.d);
     const Vec3 o_div = ray.o * inv_d;
     uint64_t stack[BVH4_STACK];
@@ -384,7 +499,11 @@ HD bool bvh_any_ww(const Node* nodes, const Prim* prims, const uint32_t* prim_ob
                 float enter, exit_;
                 bvh_child_slab(nd, c, inv_d, o_div, tmax, enter, exit_);
                 if (enter > exit_) continue;
-                if constexpr (!Node::EMPTY_BEFORE_BOX) {
+                if constexpr (Node::TAGGED) {
+                    // the word says it (the quantized node's was looked at
+                    // before its box)
+                    if (!Node::EMPTY_BEFORE_BOX && nd.child[c] == BVH4_NONE_W) continue;
+                } else {
                     // the empty-slot rule, spelled out here: as the result of
                     // a helper the && compiles to different code
                     if (nd.child[c] < 0 && nd.cnt[c] == 0) continue;
@@ -403,37 +522,36 @@ HD bool bvh_any_ww(const Node* nodes, const Prim* prims, const uint32_t* prim_ob
         if (cur == BVH4_NONE_W) return false;
         while (bvh4_is_leaf(cur)) {
             const int base = bvh4_leaf_base(cur), pc = bvh4_leaf_count(cur);
-            BVH_LEAF_ANY_RETURN(prims, prim_obj, ray, base, pc, tmax)
+            BVH_LEAF_ANY_RETURN(prims, prim_obj, ray, base, pc, tmax, tri_only)
             BVH_POP_WORD(cur, stack, sp, lds_slot, lds_n, break)
         }
         if (cur == BVH4_NONE_W) return false;
     }
 }
 
-HD HitRecord ray_intersect_bvh4_ww(const BVH4Node* nodes,
+HD HitRecord ray_intersect_bvh4_ww(const BVH4NodeT* nodes,
                                    const Prim* prims, const uint32_t* prim_obj,
                                    const Ray& ray, float tmax,
-                                   uint64_t* lds_slot = nullptr, int lds_n = 0,
-                                   const BVH4Node* top_cache = nullptr,
+                                   LdsSlot lds_slot = nullptr, int lds_n = 0,
+                                   const BVH4NodeT* top_cache = nullptr,
                                    int n_cached = 0, bool tri_only = false) {
     return bvh_closest_ww(nodes, prims, prim_obj, ray, tmax, lds_slot, lds_n,
                           top_cache, n_cached, tri_only);
 }
-// (tri_only is taken for call-site symmetry; see BVH_LEAF_ANY_RETURN)
-HD bool occlusion_test_bvh4_ww(const BVH4Node* nodes,
+HD bool occlusion_test_bvh4_ww(const BVH4NodeT* nodes,
                                const Prim* prims, const uint32_t* prim_obj,
                                const Ray& ray, float tmax,
-                               uint64_t* lds_slot = nullptr, int lds_n = 0,
-                               const BVH4Node* top_cache = nullptr,
-                               int n_cached = 0, bool /*tri_only*/ = false) {
+                               LdsSlot lds_slot = nullptr, int lds_n = 0,
+                               const BVH4NodeT* top_cache = nullptr,
+                               int n_cached = 0, bool tri_only = false) {
     return bvh_any_ww(nodes, prims, prim_obj, ray, tmax, lds_slot, lds_n,
-                      top_cache, n_cached);
+                      top_cache, n_cached, tri_only);
 }
 // The same two walks over the quantized tree.
 HD HitRecord ray_intersect_bvh4q_ww(const BVH4NodeQ* nodes,
                                     const Prim* prims, const uint32_t* prim_obj,
                                     const Ray& ray, float tmax,
-                                    uint64_t* lds_slot = nullptr, int lds_n = 0,
+                                    LdsSlot lds_slot = nullptr, int lds_n = 0,
                                     const BVH4NodeQ* top_cache = nullptr,
                                     int n_cached = 0) {
     return bvh_closest_ww(nodes, prims, prim_obj, ray, tmax, lds_slot, lds_n,
@@ -442,11 +560,11 @@ HD HitRecord ray_intersect_bvh4q_ww(const BVH4NodeQ* nodes,
 HD bool occlusion_test_bvh4q_ww(const BVH4NodeQ* nodes,
                                 const Prim* prims, const uint32_t* prim_obj,
                                 const Ray& ray, float tmax,
-                                uint64_t* lds_slot = nullptr, int lds_n = 0,
+                                LdsSlot lds_slot = nullptr, int lds_n = 0,
                                 const BVH4NodeQ* top_cache = nullptr,
                                 int n_cached = 0) {
     return bvh_any_ww(nodes, prims, prim_obj, ray, tmax, lds_slot, lds_n,
-                      top_cache, n_cached);
+                      top_cache, n_cached, false);
 }
 
 // ------------------------------------------------------ inline-leaf walks
@@ -457,7 +575,7 @@ HD bool occlusion_test_bvh4q_ww(const BVH4NodeQ* nodes,
 HD HitRecord ray_intersect_bvh4(const BVH4Node* nodes,
                                 const Prim* prims, const uint32_t* prim_obj,
                                 const Ray& ray, float tmax = MAX_DIST,
-                                uint64_t* lds_slot = nullptr, int lds_n = 0) {
+                                LdsSlot lds_slot = nullptr, int lds_n = 0) {
     HitRecord rec;
     rec.t = tmax;
     const Vec3 inv_d = safe_rcp_dir(ray.d);
@@ -494,7 +612,7 @@ HD HitRecord ray_intersect_bvh4(const BVH4Node* nodes,
 template <int W>
 HD bool bvh_any_inline(const BVHWideNode<W>* nodes, const Prim* prims,
                        const uint32_t* prim_obj, const Ray& ray, float tmax,
-                       uint64_t* lds_slot, int lds_n) {
+                       LdsSlot lds_slot, int lds_n) {
     const Vec3 inv_d = safe_rcp_dir(ray.d);
     const Vec3 o_div = ray.o * inv_d;
     uint64_t stack[BVH4_STACK];
@@ -511,7 +629,7 @@ HD bool bvh_any_inline(const BVHWideNode<W>* nodes, const Prim* prims,
             const int ch = nd.child[c];
             if (ch < 0) {
                 const int base = ~ch, pc = nd.cnt[c];
-                BVH_LEAF_ANY_RETURN(prims, prim_obj, ray, base, pc, tmax)
+                BVH_LEAF_ANY_RETURN(prims, prim_obj, ray, base, pc, tmax, false)
             } else if (cur == BVH4_NONE_W) {
                 cur = (uint32_t)ch;
             } else {
@@ -525,7 +643,7 @@ HD bool bvh_any_inline(const BVHWideNode<W>* nodes, const Prim* prims,
 HD bool occlusion_test_bvh4(const BVH4Node* nodes,
                             const Prim* prims, const uint32_t* prim_obj,
                             const Ray& ray, float tmax,
-                            uint64_t* lds_slot = nullptr, int lds_n = 0) {
+                            LdsSlot lds_slot = nullptr, int lds_n = 0) {
     return bvh_any_inline(nodes, prims, prim_obj, ray, tmax, lds_slot, lds_n);
 }
 
@@ -541,7 +659,7 @@ HD Vec2 bvh4_cost(const BVH4Node* nodes, const Prim* prims,
     rec.t = MAX_DIST;
     int node_visits = 0, prim_tests = 0;
     uint32_t stack[BVH4_STACK];
-    uint64_t* const no_lds = nullptr;
+    const LdsSlot no_lds = nullptr;
     int sp = 0;
     uint32_t cur = 0;
     while (cur != BVH4_NONE_W) {
@@ -595,12 +713,13 @@ HD void bvh4_walk_init(Bvh4Walk& w, const Ray& ray, float tmax) {
 
 // One step: a node visit (test 4 children, descend/push) OR one leaf batch.
 // Returns true while the walk still has work.
-HD bool bvh4_walk_step(Bvh4Walk& w, const BVH4Node* nodes, const Prim* prims,
-                       const uint32_t* prim_obj, uint64_t* lds_slot, int lds_n) {
+HD bool bvh4_walk_step(Bvh4Walk& w, const BVH4NodeT* nodes, const Prim* prims,
+                       const uint32_t* prim_obj, LdsSlot lds_slot, int lds_n) {
     if (w.cur == BVH4_NONE_W) return false;
     if (bvh4_not_leaf(w.cur)) {
-        const BVH4Node nd = nodes[w.cur];
-        BVH_VISIT_ORDERED(BVH4Node, next, nd, w.inv_d, w.o_div, w.rec.t,
+        const BVH4NodeT nd = nodes[w.cur];
+        uint32_t next;
+        BVH_VISIT_TAGGED4(next, nd, w.inv_d, w.o_div, w.rec.t,
                           w.stack, w.sp, lds_slot, lds_n)
         if (next != BVH4_NONE_W) { w.cur = next; return true; }
     } else {
@@ -608,6 +727,22 @@ HD bool bvh4_walk_step(Bvh4Walk& w, const BVH4Node* nodes, const Prim* prims,
                       bvh4_leaf_count(w.cur), w.rec);
     }
     BVH_POP_CLOSER(w.cur, w.stack, w.sp, lds_slot, lds_n, w.rec.t, return false, return true)
+}
+
+// Host-side conversion BVH4Node -> traversal node: boxes copied, every slot's
+// word tagged once here instead of on every visit.
+inline std::vector<BVH4NodeT> tag_bvh4(const BVH4Node* nodes, int n) {
+    std::vector<BVH4NodeT> out((size_t)(n > 0 ? n : 0));
+    for (int i = 0; i < n; ++i) {
+        const BVH4Node& s = nodes[i];
+        BVH4NodeT& t = out[i];
+        std::memcpy(t.lo_x, s.lo_x, 6 * 4 * sizeof(float));
+        for (int c = 0; c < 4; ++c) {
+            t.child[c] = bvh4_child_word(s.child[c], s.cnt[c]);
+            t.pad[c] = 0;
+        }
+    }
+    return out;
 }
 
 // Host-side conversion fp32 4-wide -> quantized (outward rounding).

@@ -31,7 +31,7 @@ HD uint32_t bvh_child_word_at(const BVH8Node& nd, uint32_t slot) {
 HD HitRecord ray_intersect_bvh8_ww(const BVH8Node* nodes,
                                    const Prim* prims, const uint32_t* prim_obj,
                                    const Ray& ray, float tmax,
-                                   uint64_t* lds_slot = nullptr, int lds_n = 0) {
+                                   LdsSlot lds_slot = nullptr, int lds_n = 0) {
     return bvh_closest_ww(nodes, prims, prim_obj, ray, tmax, lds_slot, lds_n,
                           (const BVH8Node*)nullptr, 0, false);
 }
@@ -40,7 +40,7 @@ HD HitRecord ray_intersect_bvh8_ww(const BVH8Node* nodes,
 HD bool occlusion_test_bvh8(const BVH8Node* nodes,
                             const Prim* prims, const uint32_t* prim_obj,
                             const Ray& ray, float tmax,
-                            uint64_t* lds_slot = nullptr, int lds_n = 0) {
+                            LdsSlot lds_slot = nullptr, int lds_n = 0) {
     return bvh_any_inline(nodes, prims, prim_obj, ray, tmax, lds_slot, lds_n);
 }
 

@@ -46,6 +46,7 @@ struct SceneView {
     // the collapse source; traversal runs on the 4-wide tree when present)
     const BVHNode* nodes; int n_nodes;
     const BVH4Node* nodes4; int n_nodes4;
+    const BVH4NodeT* nodes4t;               // tagged mirror: what the walks load
     const BVH4NodeQ* nodes4q;               // quantized mirror (HIPPT_QBVH)
     const BVH8Node* nodes8; int n_nodes8;   // A/B: used when non-null
     const Prim* prims; const PrimAttr* attrs; const uint32_t* prim_obj; int n_prims;
@@ -136,11 +137,11 @@ HD int pick_emitter(const SceneView& sv, Sampler& sp, float& pdf) {
 #ifdef HIPPT_QBVH
 using TravNode = BVH4NodeQ;
 #else
-using TravNode = BVH4Node;
+using TravNode = BVH4NodeT;   // nodes4 with pre-tagged child words (bvh4.h)
 #endif
 
 struct TravCtx {
-    uint64_t* lds_slot = nullptr;
+    LdsSlot lds_slot = nullptr;           // LDS-typed on the device (bvh4.h)
     int lds_n = 0;
     const TravNode* top_cache = nullptr;  // LDS copy of the tree top
     int n_cached = 0;
@@ -150,7 +151,7 @@ HD const TravNode* trav_nodes(const SceneView& sv) {
 #ifdef HIPPT_QBVH
     return sv.nodes4q;
 #else
-    return sv.nodes4;
+    return sv.nodes4t;
 #endif
 }
 
@@ -170,7 +171,7 @@ HD HitRecord scene_intersect(const SceneView& sv, const Ray& ray,
     return ray_intersect_bvh4q_ww(sv.nodes4q, sv.prims, sv.prim_obj, ray, tmax,
                                   tc.lds_slot, tc.lds_n, tc.top_cache, tc.n_cached);
 #else
-    return ray_intersect_bvh4_ww(sv.nodes4, sv.prims, sv.prim_obj, ray, tmax,
+    return ray_intersect_bvh4_ww(sv.nodes4t, sv.prims, sv.prim_obj, ray, tmax,
                                  tc.lds_slot, tc.lds_n, tc.top_cache, tc.n_cached,
                                  sv.tri_only != 0);
 #endif
@@ -183,7 +184,7 @@ HD bool scene_occluded(const SceneView& sv, const Ray& ray, float tmax,
     return occlusion_test_bvh4q_ww(sv.nodes4q, sv.prims, sv.prim_obj, ray, tmax,
                                    tc.lds_slot, tc.lds_n, tc.top_cache, tc.n_cached);
 #else
-    return occlusion_test_bvh4_ww(sv.nodes4, sv.prims, sv.prim_obj, ray, tmax,
+    return occlusion_test_bvh4_ww(sv.nodes4t, sv.prims, sv.prim_obj, ray, tmax,
                                   tc.lds_slot, tc.lds_n, tc.top_cache, tc.n_cached,
                                   sv.tri_only != 0);
 #endif

@@ -57,7 +57,7 @@ void k_render(SceneView sv, float* __restrict__ accum, float* __restrict__ var,
     for (int i = tid; i < n_cached * NW; i += 256)
         ((uint64_t*)s_cache)[i] = ((const uint64_t*)trav_nodes(sv))[i];
     if (n_cached > 0) __syncthreads();
-    TravCtx tc{&s_base[tid], lds_n, s_cache, n_cached};
+    TravCtx tc{(LdsSlot)&s_base[tid], lds_n, s_cache, n_cached};
     int tile = blockIdx.y * gridDim.x + blockIdx.x;
     if (swiz) tile = xcd_swizzle(tile, gridDim.x * gridDim.y);
     const int px = (tile % gridDim.x) * 16 + threadIdx.x;
@@ -133,7 +133,7 @@ void k_render_persistent(SceneView sv, float* __restrict__ accum, float* __restr
                          int spp0, int nspp, uint32_t seed, uint32_t* work_counter,
                          int tiles_x, int n_tiles, int lds_n) {
     extern __shared__ uint64_t s_stk[];
-    TravCtx tc{&s_stk[threadIdx.y * 16 + threadIdx.x], lds_n};
+    TravCtx tc{(LdsSlot)&s_stk[threadIdx.y * 16 + threadIdx.x], lds_n};
     __shared__ uint32_t s_tile;
     for (;;) {
         if (threadIdx.x == 0 && threadIdx.y == 0)
@@ -173,7 +173,7 @@ void k_render_lt(SceneView sv, float* __restrict__ accum,
                  long long n_paths, int spp0, int nspp, uint32_t seed,
                  int spec_constraint, float caustic_scaling, int lds_n) {
     extern __shared__ uint64_t s_stk[];
-    TravCtx tc{&s_stk[threadIdx.x], lds_n};
+    TravCtx tc{(LdsSlot)&s_stk[threadIdx.x], lds_n};
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_paths; i += stride) {
         Sampler sp(uint32_t(i & 0xffffffff), uint32_t(spp0) * SEED_SCALER + seed + uint32_t(i >> 32));
@@ -206,15 +206,21 @@ int launch_render(const SceneView& sv, float* accum, float* var,
     auto swiz = [] { return swiz_v; };
     // Two decoupled knobs (defaults from same-box A/B on MI355X, see
     // profiles/README.md):
-    //   HIPPT_OCC   = __launch_bounds__ min waves/SIMD {3,4,5,6,8}.  The
-    //   register CAP is what the walk wants (waves 6 spills VGPRs yet was
-    //   measured ~1.5x over the compiler's natural allocation).  Default 6.
+    //   HIPPT_OCC   = waves/SIMD the kernel is pinned to (amdgpu_waves_per_eu
+    //   instantiation: pt {3,4,5,6,8}, vpt {4,6}) and the LDS budget that
+    //   goes with it.  The optimum differs per renderer, so each has a
+    //   compiled-in default of its own (OCC_PT / OCC_VPT; the other
+    //   renderers keep the budget of 4); the env var overrides all of them.
     //   HIPPT_STACK = lds | scratch: where the BVH4 traversal stack lives
     //   (LDS entries sized {26,20,16,12,12} for occ {3,4,5,6,8}).
-    static int occ_v = [] {
-        const char* e = getenv("HIPPT_OCC");
-        return e ? atoi(e) : 4;   // ww walk: occ4 measured 140.6 vs 128.9 @6
-    }();
+    constexpr int OCC_PT = 4, OCC_VPT = 4, OCC_REST = 4;
+    static const char* occ_env = getenv("HIPPT_OCC");
+    static int occ_env_v = occ_env ? atoi(occ_env) : 0;
+    const bool is_rest = renderer == R_LIGHT_TRACE || renderer == R_DEPTH ||
+                         renderer == R_BVH_COST || renderer == R_MEGAKERNEL_PT_DYN;
+    const int occ_v = occ_env ? occ_env_v
+                    : renderer == R_VOLUME_PT ? OCC_VPT
+                    : is_rest ? OCC_REST : OCC_PT;
     // HIPPT_TOPCACHE = nodes of the tree top copied to LDS per block
     // (default 64 = 8 KB); the stack's LDS share shrinks to keep the same
     // per-block LDS budget (occupancy unchanged).
@@ -229,11 +235,12 @@ int launch_render(const SceneView& sv, float* accum, float* var,
     // keep at least 4 LDS stack entries per thread alongside the cache
     int cache_cap = (20 * 256 * 8 - 4 * 256 * 8) / (int)sizeof(TravNode);
     if (n_cached > cache_cap) n_cached = cache_cap;
-    static int lds_budget = [] {
+    static int stack_in_lds = [] {
         const char* e = getenv("HIPPT_STACK");
-        if (e && strcmp(e, "scratch") == 0) return 0;   // default: lds
-        return (occ_v <= 3 ? 26 : occ_v == 4 ? 20 : occ_v == 5 ? 16 : 12) * 256 * 8;
+        return (e && strcmp(e, "scratch") == 0) ? 0 : 1;   // default: lds
     }();
+    const int lds_budget = stack_in_lds
+        ? (occ_v <= 3 ? 26 : occ_v == 4 ? 20 : occ_v == 5 ? 16 : 12) * 256 * 8 : 0;
     const int lds_n = lds_budget > 0
         ? (lds_budget - n_cached * (int)sizeof(TravNode)) / (256 * 8) : 0;
     const uint32_t shmem = (uint32_t)(lds_n * 256 * 8 + n_cached * (int)sizeof(TravNode));

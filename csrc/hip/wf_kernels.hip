@@ -89,7 +89,7 @@ __device__ __forceinline__ TravCtx wf_lds_ctx(const SceneView& sv, uint64_t* s_s
     for (int i = threadIdx.x; i < n_cached * NW; i += 256)
         ((uint64_t*)s_cache)[i] = ((const uint64_t*)trav_nodes(sv))[i];
     if (n_cached > 0) __syncthreads();
-    return TravCtx{&s_base[threadIdx.x], lds_n, s_cache, n_cached};
+    return TravCtx{(LdsSlot)&s_base[threadIdx.x], lds_n, s_cache, n_cached};
 }
 
 // ----------------------------------------------------------------- raygen
@@ -453,8 +453,8 @@ void k_wf_trace_dual(SceneView sv, WfState st, const uint32_t* __restrict__ orde
     const int k0 = blockIdx.x * blockDim.x + tid;
     const int k1 = k0 + half;
     const int lds_half = lds_n >> 1;
-    uint64_t* slot0 = &s_stk[tid];
-    uint64_t* slot1 = &s_stk[tid + (size_t)lds_half * BVH4_LDS_STRIDE];
+    LdsSlot slot0 = (LdsSlot)&s_stk[tid];
+    LdsSlot slot1 = (LdsSlot)&s_stk[tid + (size_t)lds_half * BVH4_LDS_STRIDE];
     const int i0 = k0 < half ? (int)(order[k0] & 0x00FFFFFFu) : 0;
     const int i1 = k1 < live ? (int)(order[k1] & 0x00FFFFFFu) : 0;
     bool a0 = k0 < half && (st.status[i0] >> 24) < DEAD;
@@ -477,8 +477,8 @@ void k_wf_trace_dual(SceneView sv, WfState st, const uint32_t* __restrict__ orde
     }
     bool r0 = a0, r1 = a1;
     while (r0 | r1) {
-        if (r0) r0 = bvh4_walk_step(w0, sv.nodes4, sv.prims, sv.prim_obj, slot0, lds_half);
-        if (r1) r1 = bvh4_walk_step(w1, sv.nodes4, sv.prims, sv.prim_obj, slot1, lds_half);
+        if (r0) r0 = bvh4_walk_step(w0, sv.nodes4t, sv.prims, sv.prim_obj, slot0, lds_half);
+        if (r1) r1 = bvh4_walk_step(w1, sv.nodes4t, sv.prims, sv.prim_obj, slot1, lds_half);
     }
     if (a0) wf_trace_finish(sv, st, i0, ray0, pdf0, w0.rec);
     if (a1) wf_trace_finish(sv, st, i1, ray1, pdf1, w1.rec);

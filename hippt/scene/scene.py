@@ -490,7 +490,9 @@ class Scene:
         GPU in the wavefront kernels' LDS layout, where lds_n (LDS stack
         entries per thread) and n_cached (top-tree nodes kept in LDS)
         default to the render launcher's own values (-1) and explicit
-        values pass through its clamps.  Returns (t, prim, u, v, occluded);
+        values pass through its clamps.  On the host lds_n > 0 keeps the
+        bottom lds_n stack entries in a strided buffer standing in for LDS.
+        Returns (t, prim, u, v, occluded);
         prim indexes the BVH-ordered primitive array, -1 on a miss."""
         o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
