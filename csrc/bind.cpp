@@ -8,6 +8,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/numpy.h>
 #include <pybind11/stl.h>
+#include <algorithm>
 #include <cstring>
 #include <stdexcept>
 
@@ -1014,6 +1015,64 @@ int py_bvh4_visit_selftest(farr nodes4, farr ray_o, farr ray_d, float tmax) {
     return bad;
 }
 
+// Any-hit node-visit self-test: for every (ray, node) pair one visit child by
+// child (BVH_VISIT_ANY_EACH on the BVH4Node) and one in a straight line
+// (BVH_VISIT_ANY4 on the tagged node), each on an empty private stack against the same tmax.
+// The two may order the children differently, so they are compared as sets:
+// {next} and the pushed words, without misses, must be the same words, none
+// twice, and no BVH4_NONE_W (or miss value) pushed.  Returns the number of
+// mismatching pairs.
+int py_bvh4_any_visit_selftest(farr nodes4, farr ray_o, farr ray_d, float tmax) {
+    if (nodes4.ndim() != 2 || nodes4.shape(1) != 32) throw std::runtime_error("nodes4 must be (m,32)");
+    const BVH4Node* n4 = (const BVH4Node*)nodes4.data();
+    const int nn = (int)nodes4.shape(0);
+    const std::vector<BVH4NodeT> t4 = tag_bvh4(n4, nn);
+    const LdsSlot no_lds = nullptr;
+    // the words of one visit, sorted; false if one is pushed that must not be
+    auto collect = [](uint32_t next, const uint64_t* st, int sp, uint32_t* out, int& n) {
+        n = 0;
+        if (next != BVH4_NONE_W) out[n++] = next;
+        for (int k = 0; k < sp; ++k) {
+            if (st[k] >> 32) return false;
+            const uint32_t w = (uint32_t)st[k];
+            if (w == BVH4_NONE_W || w == BVH4_ANY_MISS_W) return false;
+            out[n++] = w;
+        }
+        std::sort(out, out + n);
+        return std::adjacent_find(out, out + n) == out + n;
+    };
+    int bad = 0;
+    const int nr = (int)ray_o.shape(0);
+    for (int i = 0; i < nr; ++i) {
+        Ray r;
+        r.o = {ray_o.at(i, 0), ray_o.at(i, 1), ray_o.at(i, 2)};
+        r.d = {ray_d.at(i, 0), ray_d.at(i, 1), ray_d.at(i, 2)};
+        const Vec3 inv_d = safe_rcp_dir(r.d);
+        const Vec3 o_div = r.o * inv_d;
+        for (int j = 0; j < nn; ++j) {
+            uint64_t sa[4] = {0, 0, 0, 0}, sb[4] = {0, 0, 0, 0};
+            int spa = 0, spb = 0;
+            uint32_t na = BVH4_NONE_W, nb = BVH4_NONE_W;
+            {
+                const BVH4Node nd = n4[j];
+                BVH_VISIT_ANY_EACH(BVH4Node, na, nd, inv_d, o_div, tmax, sa, spa, no_lds, 0)
+            }
+            {
+                const BVH4NodeT nd = t4[j];
+                BVH_VISIT_ANY4(nb, nd, inv_d, o_div, tmax, sb, spb, no_lds, 0)
+            }
+            uint32_t wa[4], wb[4];
+            int ca, cb;
+            const bool oka = collect(na, sa, spa, wa, ca);
+            const bool okb = collect(nb, sb, spb, wb, cb);
+            // pushes only behind a next
+            const bool shape = (na != BVH4_NONE_W || spa == 0) && (nb != BVH4_NONE_W || spb == 0);
+            if (!oka || !okb || !shape || ca != cb || !std::equal(wa, wa + ca, wb)) ++bad;
+        }
+    }
+    return bad;
+}
+
 // Closest-hit query over the BVH4 tree: returns (t, prim) arrays for rays.
 py::tuple py_bvh4_hit(farr prims, uarr prim_obj, farr nodes4,
                       farr ray_o, farr ray_d) {
@@ -1160,6 +1219,8 @@ PYBIND11_MODULE(_C, m) {
     m.def("bvh4_hit", &py_bvh4_hit);
     m.def("bvh4_tag", &py_bvh4_tag, py::arg("nodes4"));
     m.def("bvh4_visit_selftest", &py_bvh4_visit_selftest, py::arg("nodes4"),
+          py::arg("ray_o"), py::arg("ray_d"), py::arg("tmax"));
+    m.def("bvh4_any_visit_selftest", &py_bvh4_any_visit_selftest, py::arg("nodes4"),
           py::arg("ray_o"), py::arg("ray_d"), py::arg("tmax"));
     m.def("bsdf_check", &py_bsdf_check);
     m.def("env_check", &py_env_check);

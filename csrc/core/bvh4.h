@@ -41,6 +41,8 @@
 // device walks run on BVH4NodeT and visit it with BVH_VISIT_TAGGED4, the
 // branch-free width-4 form of the ordered visit; the BVH4Node forms stay for
 // the host walks, width 8 and as the other side of C.bvh4_visit_selftest.
+// What latency is left sits in the leaf loops, which therefore read the
+// whole primitive at once and wait for it once (bvh_load_prim).
 //
 // Which walks a kernel can reach in the default build:
 //   ray_intersect_bvh4_ww, occlusion_test_bvh4_ww   every render kernel
@@ -51,6 +53,7 @@
 // (device code only when built with HIPPT_QBVH=1), and the 8-wide walks of
 // bvh8.h.
 #pragma once
+#include <stdexcept>
 #include "bvh.h"
 
 namespace hippt {
@@ -400,19 +403,141 @@ constexpr uint32_t BVH4_MISS_KEY = 0xffffffffu;
         BVH_VISIT_ORDERED(Node, next, nd, inv_d, o_div, tmax, stack, sp, lds_slot, lds_n) \
     }
 
+// Any-hit visit of node nd, one child after the other: the first hit child
+// becomes next, the others are pushed as bare words.  next must come in as
+// BVH4_NONE_W.  The visit the any-hit walk runs, and the other side of
+// C.bvh4_any_visit_selftest.
+#define BVH_VISIT_ANY_EACH(Node, next, nd, inv_d, o_div, tmax, stack, sp, lds_slot, lds_n) \
+    _Pragma("unroll")                                                                  \
+    for (int c_ = 0; c_ < Node::WIDTH; ++c_) {                                         \
+        if (bvh_slot_known_empty(nd, c_)) continue;                                    \
+        float enter_, exit_;                                                           \
+        bvh_child_slab(nd, c_, inv_d, o_div, tmax, enter_, exit_);                     \
+        if (enter_ > exit_) continue;                                                  \
+        if constexpr (Node::TAGGED) {                                                  \
+            /* the word says it (the quantized node's was looked at before its box) */ \
+            if (!Node::EMPTY_BEFORE_BOX && nd.child[c_] == BVH4_NONE_W) continue;      \
+        } else {                                                                       \
+            /* the empty-slot rule, spelled out here: as the result of a helper the    \
+               && compiles to different code */                                        \
+            if (nd.child[c_] < 0 && nd.cnt[c_] == 0) continue;                         \
+        }                                                                              \
+        const uint32_t lo_ = bvh_filled_child_word(nd, c_);                            \
+        if (next == BVH4_NONE_W) {                                                     \
+            next = lo_;                                                                \
+        } else {                                                                       \
+            uint64_t e_ = (uint64_t)lo_;                                               \
+            BVH_PUSH(stack, sp, lds_slot, lds_n, e_)                                   \
+        }                                                                              \
+    }
+
+// The any-hit visit for a width-4 node of tagged words, in a straight line:
+// a measured experiment that lost, kept host-tested behind BVH4_ANY_STRAIGHT.
+// The any-hit walk returns a predicate — some prim of some reached leaf has
+// EPSILON < t < tmax, tmax fixed for the whole walk — and does not cull on
+// pop, so the order in which hit children are continued and pushed cannot
+// change its result, and bare words are all it needs: no t_near key, no
+// select tree.  Each child's value is its word if the box is hit, else a miss
+// value; the four values go through the same 5-comparator min/max network as
+// the keys of BVH_VISIT_TAGGED4, which compacts the hit words to the front;
+// next is the first, the other three are pushed behind one test each.
+// What BVH_VISIT_TAGGED4 gained over the ordered visit does not carry over:
+// the form above has no key array, no sort and no push loop to lose, the
+// compiler already turns it into three push sites, and a shadow ray misses
+// most boxes, so its blocks are mostly skipped, while the network always
+// runs.  gfx950 node phase of k_wf_shadow<4>: 205 -> 203 instructions;
+// flagship 0.6% slower (profiles/README.md).
+//
+// The miss value and the comparison decide what comes first:
+//   false: miss 0xffffffff, unsigned order: internal nodes, then leaves,
+//          then misses — leaves are postponed, as the phase batching of the
+//          while-while walk wants.  An empty slot's word (BVH4_NONE_W) lies
+//          between nodes and leaves and is folded into the miss value.
+//   true:  miss BVH4_NONE_W, signed order: leaves, then nodes, then misses
+//          — prims are tested early, which favours the early exit.
+// Leaves first measured another 0.6% slower than nodes first.
+constexpr bool BVH4_ANY_STRAIGHT = false;
+constexpr bool BVH4_ANY_LEAVES_FIRST = false;
+constexpr uint32_t BVH4_ANY_MISS_W = BVH4_ANY_LEAVES_FIRST ? BVH4_NONE_W : 0xffffffffu;
+// 0xffffffff is the word of a leaf of 15 prims at base 2^27-1.  No leaf has
+// it as long as all prims lie below index BVH4_MAX_PRIMS (tag_bvh4 checks).
+constexpr int BVH4_MAX_PRIMS = 0x07ffffff;
+static_assert(BVH4_ANY_LEAVES_FIRST ||
+              BVH4_ANY_MISS_W == (0x80000000u | (15u << 27) | (uint32_t)BVH4_MAX_PRIMS),
+              "the any-hit miss value must be the one leaf word no tree holds");
+#define BVH_ANY_WORD4(w, nd, c, inv_d, o_div, tmax)                       \
+    uint32_t w;                                                           \
+    {                                                                     \
+        float enter_, exit_;                                              \
+        bvh_child_slab(nd, c, inv_d, o_div, tmax, enter_, exit_);         \
+        const bool hit_ = !bvh_slot_known_empty(nd, c) && enter_ <= exit_; \
+        if constexpr (BVH4_ANY_LEAVES_FIRST)                              \
+            w = hit_ ? nd.child[c] : BVH4_NONE_W;                         \
+        else                                                              \
+            w = hit_ && nd.child[c] != BVH4_NONE_W ? nd.child[c] : BVH4_ANY_MISS_W; \
+    }
+#define BVH_ANY_MINMAX(a, b)                                              \
+    if constexpr (BVH4_ANY_LEAVES_FIRST) {                                \
+        const uint32_t lo_ = (int32_t)(a) < (int32_t)(b) ? (a) : (b);     \
+        const uint32_t hi_ = (int32_t)(a) < (int32_t)(b) ? (b) : (a);     \
+        (a) = lo_; (b) = hi_;                                             \
+    } else BVH_KEY_MINMAX(a, b)
+#define BVH_PUSH_ANY4(w, stack, sp, lds_slot, lds_n)                      \
+    if ((w) != BVH4_ANY_MISS_W) {                                         \
+        uint64_t e_ = (uint64_t)(w);                                      \
+        BVH_PUSH(stack, sp, lds_slot, lds_n, e_)                          \
+    }
+#define BVH_VISIT_ANY4(next, nd, inv_d, o_div, tmax, stack, sp, lds_slot, lds_n) \
+    BVH_ANY_WORD4(w0_, nd, 0, inv_d, o_div, tmax)                         \
+    BVH_ANY_WORD4(w1_, nd, 1, inv_d, o_div, tmax)                         \
+    BVH_ANY_WORD4(w2_, nd, 2, inv_d, o_div, tmax)                         \
+    BVH_ANY_WORD4(w3_, nd, 3, inv_d, o_div, tmax)                         \
+    BVH_ANY_MINMAX(w0_, w1_)                                              \
+    BVH_ANY_MINMAX(w2_, w3_)                                              \
+    BVH_ANY_MINMAX(w0_, w2_)                                              \
+    BVH_ANY_MINMAX(w1_, w3_)                                              \
+    BVH_ANY_MINMAX(w1_, w2_)                                              \
+    BVH_PUSH_ANY4(w3_, stack, sp, lds_slot, lds_n)                        \
+    BVH_PUSH_ANY4(w2_, stack, sp, lds_slot, lds_n)                        \
+    BVH_PUSH_ANY4(w1_, stack, sp, lds_slot, lds_n)                        \
+    next = w0_ == BVH4_ANY_MISS_W ? BVH4_NONE_W : w0_;
+
 // ------------------------------------------------------------- leaf loops
 // Intersect prims [base, base+cnt) and tighten rec.  tri_only (a scene-
 // uniform scalar) skips the per-prim prim_obj sphere-bit load entirely —
 // the reference's TRIANGLE_ONLY compile flag ("10% faster", defines.cuh:
 // 26-27) as a runtime-free SGPR branch.
+//
+// Both loops read the whole primitive into locals first (bvh_load_prim):
+// three 16-byte loads issued together, with the sphere-bit load when there is
+// one, and one wait for all of them.  Left to itself the compiler loads e1
+// and e2, waits, tests det, and only behind that branch loads v0 and waits
+// again: two dependent round trips per triangle, three with the sphere bit.
+HD Prim bvh_load_prim(const Prim* prims, const uint32_t* prim_obj, int pid,
+                      bool tri_only, bool& sph) {
+    uint32_t obj = 0;
+    if (!tri_only) obj = prim_obj[pid];
+    const Prim p = prims[pid];
+#if HIPPT_ON_DEVICE
+    // An empty statement that reads all thirteen values: every load is
+    // issued and has landed here, none can be narrowed or sunk behind the
+    // det branch of intersect_triangle.  It emits no instruction.
+    asm volatile("" :: "v"(obj), "v"(p.v0.x), "v"(p.v0.y), "v"(p.v0.z), "v"(p.v0.w),
+                       "v"(p.e1.x), "v"(p.e1.y), "v"(p.e1.z), "v"(p.e1.w),
+                       "v"(p.e2.x), "v"(p.e2.y), "v"(p.e2.z), "v"(p.e2.w));
+#endif
+    sph = (obj & PRIM_SPHERE_BIT) != 0;
+    return p;
+}
 HD void bvh4_leaf_hit(const Prim* prims, const uint32_t* prim_obj,
                       const Ray& ray, int base, int cnt, HitRecord& rec,
                       bool tri_only = false) {
     for (int k = 0; k < cnt; ++k) {
         int pid = base + k;
-        bool sph = !tri_only && (prim_obj[pid] & PRIM_SPHERE_BIT) != 0;
+        bool sph;
+        const Prim p = bvh_load_prim(prims, prim_obj, pid, tri_only, sph);
         float u, v;
-        float t = intersect_prim(prims[pid], sph, ray, u, v);
+        float t = intersect_prim(p, sph, ray, u, v);
         if (t > EPSILON && t < rec.t) {
             rec.t = t; rec.u = u; rec.v = v; rec.prim_idx = pid;
         }
@@ -424,9 +549,10 @@ HD void bvh4_leaf_hit(const Prim* prims, const uint32_t* prim_obj,
 #define BVH_LEAF_ANY_RETURN(prims, prim_obj, ray, base, cnt, tmax, tri_only)  \
     for (int k_ = 0; k_ < (cnt); ++k_) {                                      \
         int pid_ = (base) + k_;                                               \
-        bool sph_ = !(tri_only) && ((prim_obj)[pid_] & PRIM_SPHERE_BIT) != 0; \
+        bool sph_;                                                            \
+        const Prim p_ = bvh_load_prim(prims, prim_obj, pid_, tri_only, sph_); \
         float u_, v_;                                                         \
-        float t_ = intersect_prim((prims)[pid_], sph_, ray, u_, v_);          \
+        float t_ = intersect_prim(p_, sph_, ray, u_, v_);                     \
         if (t_ > EPSILON && t_ < (tmax)) return true;                         \
     }
 
@@ -493,28 +619,10 @@ HD bool bvh_any_ww(const Node* nodes, const Prim* prims, const uint32_t* prim_ob
             const Node* nsrc = (int)cur < n_cached ? top_cache : nodes;
             const Node nd = nsrc[cur];
             uint32_t next = BVH4_NONE_W;
-#pragma unroll
-            for (int c = 0; c < Node::WIDTH; ++c) {
-                if (bvh_slot_known_empty(nd, c)) continue;
-                float enter, exit_;
-                bvh_child_slab(nd, c, inv_d, o_div, tmax, enter, exit_);
-                if (enter > exit_) continue;
-                if constexpr (Node::TAGGED) {
-                    // the word says it (the quantized node's was looked at
-                    // before its box)
-                    if (!Node::EMPTY_BEFORE_BOX && nd.child[c] == BVH4_NONE_W) continue;
-                } else {
-                    // the empty-slot rule, spelled out here: as the result of
-                    // a helper the && compiles to different code
-                    if (nd.child[c] < 0 && nd.cnt[c] == 0) continue;
-                }
-                const uint32_t lo = bvh_filled_child_word(nd, c);
-                if (next == BVH4_NONE_W) {
-                    next = lo;
-                } else {
-                    uint64_t e = (uint64_t)lo;
-                    BVH_PUSH(stack, sp, lds_slot, lds_n, e)
-                }
+            if constexpr (BVH4_ANY_STRAIGHT && Node::WIDTH == 4 && Node::TAGGED) {
+                BVH_VISIT_ANY4(next, nd, inv_d, o_div, tmax, stack, sp, lds_slot, lds_n)
+            } else {
+                BVH_VISIT_ANY_EACH(Node, next, nd, inv_d, o_div, tmax, stack, sp, lds_slot, lds_n)
             }
             if (next != BVH4_NONE_W) { cur = next; continue; }
             BVH_POP_WORD(cur, stack, sp, lds_slot, lds_n, break)
@@ -738,6 +846,10 @@ inline std::vector<BVH4NodeT> tag_bvh4(const BVH4Node* nodes, int n) {
         BVH4NodeT& t = out[i];
         std::memcpy(t.lo_x, s.lo_x, 6 * 4 * sizeof(float));
         for (int c = 0; c < 4; ++c) {
+            // prims below BVH4_MAX_PRIMS: the base fits its 27 bits and no
+            // leaf word is the any-hit visit's miss value
+            if (s.child[c] < 0 && (int64_t)(~s.child[c]) + s.cnt[c] > BVH4_MAX_PRIMS)
+                throw std::runtime_error("tag_bvh4: leaf beyond BVH4_MAX_PRIMS prims");
             t.child[c] = bvh4_child_word(s.child[c], s.cnt[c]);
             t.pad[c] = 0;
         }

@@ -3,7 +3,10 @@
 // Capability parity: reference src/core/ray.cuh, aabb.cuh, primitives.cuh,
 // aos.cuh (PrecomputedArray).  Layout re-designed for MI355X: each primitive
 // is 3 16-byte vectors {v0|flag, e1, e2} so a leaf test is three
-// global_load_dwordx4; spheres pack {center,radius} into v0 with a tag bit in
+// global_load_dwordx4 (the BVH4 leaf loops read it whole through
+// bvh_load_prim, bvh4.h: handed a `const Prim&` into global memory,
+// intersect_triangle compiles to two 12-byte loads, the det test, and a
+// third load behind it); spheres pack {center,radius} into v0 with a tag bit in
 // the object-index array (bit31), matching the reference's packing semantics
 // (scene.cu:902-930) without its texture-memory path.
 #pragma once
