@@ -16,6 +16,7 @@
 #include "core/integrator.h"
 #include "cpu/bvh_build.h"
 #include "hip/kernels.h"
+#include "hip/lds_plan.h"
 
 namespace py = pybind11;
 using namespace hippt;
@@ -1242,6 +1243,15 @@ PYBIND11_MODULE(_C, m) {
                              out.mutable_data(), &live));
         return py::make_tuple(out, live);
     }, py::arg("status"), py::arg("gather"), py::arg("mode"));
+    m.def("lds_plan", [](int occ, bool stack_in_lds, bool scratch_drops_cache, int n_nodes4,
+                         int node_bytes, int cache_req, int lds_req) {
+        if (n_nodes4 < 0 || node_bytes <= 0) throw std::runtime_error("lds_plan: bad sizes");
+        const LdsPlan p = lds_plan(occ, stack_in_lds, scratch_drops_cache, n_nodes4,
+                                   node_bytes, cache_req, lds_req);
+        return py::make_tuple(p.lds_n, p.n_cached, p.shmem);
+    }, py::arg("occ"), py::arg("stack_in_lds"), py::arg("scratch_drops_cache"),
+       py::arg("n_nodes4"), py::arg("node_bytes"), py::arg("cache_req"),
+       py::arg("lds_req") = -1);
     m.def("dev_synchronize", [] { HIP_OK(dev_synchronize()); });
     m.def("dev_set_device", [](int d) { HIP_OK(dev_set_device(d)); });
 

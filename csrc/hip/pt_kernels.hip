@@ -8,8 +8,8 @@
 // across 8 XCDs, and a per-kernel spp loop to amortize launch overhead.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
-#include <cstdlib>
-#include <cstring>
+#include "trav_lds.h"
+#include <climits>
 #include "../core/integrator.h"
 #include "../core/integrator_vol.h"
 #include "../core/light_tracer.h"
@@ -32,11 +32,11 @@ __device__ inline int xcd_swizzle(int flat, int n_tiles) {
 }
 
 // lds_n = traversal-stack entries per thread held in (dynamic) LDS, bvh4.h.
-// The LDS block allocation (lds_n x 8 B x 256 threads) is also the occupancy
-// governor: 12/16/20/26/40 entries -> 6/5/4/3/2 waves per SIMD.
+// The LDS block allocation (lds_plan.h) is also the occupancy governor:
+// 26/20/16/12 entries -> 3/4/5/6 waves per SIMD.
 // BRICKS (R_VOLUME_PT only): the scene holds brick-layout grid media; the
 // dense-only instantiation keeps the tracking loops free of the layout test.
-template <int RENDERER, int MINW = 6, bool BRICKS = false>
+template <int RENDERER, int MINW, bool BRICKS = false>
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(MINW, MINW)))   // exact residency: the LDS
 // stack caps blocks/CU at MINW waves/SIMD, so the allocator may spend the
@@ -46,18 +46,7 @@ void k_render(SceneView sv, float* __restrict__ accum, float* __restrict__ var,
               int spp0, int nspp, uint32_t seed, int swiz, int lds_n, int n_cached, int y_off, int y_end,
               const uint8_t* __restrict__ spp_map, float* __restrict__ aux) {
     extern __shared__ uint64_t s_stk[];
-    // dynamic-LDS layout: [n_cached 128-byte nodes][per-thread stacks].
-    // The top of the tree is copied into LDS once per block: every walk's
-    // first visits are nodes 0..n_cached, and at a 95% L2 hit rate the
-    // bound is hit latency — LDS is ~4x closer.
-    constexpr int NW = (int)(sizeof(TravNode) / 8);   // u64 words per node
-    TravNode* s_cache = (TravNode*)s_stk;
-    uint64_t* s_base = s_stk + (size_t)n_cached * NW;
-    const int tid = threadIdx.y * 16 + threadIdx.x;
-    for (int i = tid; i < n_cached * NW; i += 256)
-        ((uint64_t*)s_cache)[i] = ((const uint64_t*)trav_nodes(sv))[i];
-    if (n_cached > 0) __syncthreads();
-    TravCtx tc{(LdsSlot)&s_base[tid], lds_n, s_cache, n_cached};
+    TravCtx tc = trav_lds_ctx(sv, s_stk, threadIdx.y * 16 + threadIdx.x, lds_n, n_cached);
     int tile = blockIdx.y * gridDim.x + blockIdx.x;
     if (swiz) tile = xcd_swizzle(tile, gridDim.x * gridDim.y);
     const int px = (tile % gridDim.x) * 16 + threadIdx.x;
@@ -126,7 +115,7 @@ void k_render(SceneView sv, float* __restrict__ accum, float* __restrict__ var,
 // On MI355X: grid = 256 CUs x blocks/CU, tile = 16x16 pixels, counter in
 // device memory zeroed per launch; removes the tail effect of uneven
 // per-tile path lengths on the 8-XCD chip.
-template <int RENDERER, int MINW = 6>
+template <int RENDERER, int MINW>
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(MINW, MINW)))
 void k_render_persistent(SceneView sv, float* __restrict__ accum, float* __restrict__ var,
@@ -199,56 +188,38 @@ int launch_render(const SceneView& sv, float* accum, float* var,
     // HIPPT_SWIZZLE=1 enables the XCD band swizzle (measured -14% on the
     // kitchen megakernel — the round-robin XCD dispatch already spreads
     // neighbor tiles well; default off, kept as an A/B hook)
-    static int swiz_v = [] {
-        const char* e = getenv("HIPPT_SWIZZLE");
-        return e ? atoi(e) : 0;
-    }();
-    auto swiz = [] { return swiz_v; };
+    static const int swiz_v = env_int("HIPPT_SWIZZLE", 0);
+    const int swiz = renderer == R_DEPTH || renderer == R_BVH_COST ? 0 : swiz_v;
     // Two decoupled knobs (defaults from same-box A/B on MI355X, see
     // profiles/README.md):
     //   HIPPT_OCC   = waves/SIMD the kernel is pinned to (amdgpu_waves_per_eu
-    //   instantiation: pt {3,4,5,6,8}, vpt {4,6}) and the LDS budget that
-    //   goes with it.  The optimum differs per renderer, so each has a
-    //   compiled-in default of its own (OCC_PT / OCC_VPT; the other
-    //   renderers keep the budget of 4); the env var overrides all of them.
-    //   HIPPT_STACK = lds | scratch: where the BVH4 traversal stack lives
-    //   (LDS entries sized {26,20,16,12,12} for occ {3,4,5,6,8}).
-    constexpr int OCC_PT = 4, OCC_VPT = 4, OCC_REST = 4;
-    static const char* occ_env = getenv("HIPPT_OCC");
-    static int occ_env_v = occ_env ? atoi(occ_env) : 0;
+    //   instantiation: pt {3,4,5,6,8}, vpt {4,6}, the rest 6) and the LDS
+    //   budget that goes with it (lds_plan.h).  The optimum differs
+    //   per renderer, so each has a compiled-in default of its own (OCC_PT /
+    //   OCC_VPT; the other renderers keep the budget of 4); the env var
+    //   overrides all of them.
+    //   HIPPT_STACK = lds | scratch: where the BVH4 traversal stack lives;
+    //   the top-tree cache stays in LDS either way.
+    constexpr int OCC_PT = 4, OCC_VPT = 4, OCC_REST = 4, OCC_UNSET = INT_MIN;
+    static const int occ_env = env_int("HIPPT_OCC", OCC_UNSET);
     const bool is_rest = renderer == R_LIGHT_TRACE || renderer == R_DEPTH ||
                          renderer == R_BVH_COST || renderer == R_MEGAKERNEL_PT_DYN;
-    const int occ_v = occ_env ? occ_env_v
+    const int occ_v = occ_env != OCC_UNSET ? occ_env
                     : renderer == R_VOLUME_PT ? OCC_VPT
                     : is_rest ? OCC_REST : OCC_PT;
-    // HIPPT_TOPCACHE = nodes of the tree top copied to LDS per block
-    // (default 64 = 8 KB); the stack's LDS share shrinks to keep the same
-    // per-block LDS budget (occupancy unchanged).
-    static int cache_env = [] {
-        const char* e = getenv("HIPPT_TOPCACHE");
-        return e ? atoi(e) : -1;
-    }();
-    // priority: env A/B hook > accelerator XML cache_level > measured default
-    int cache_req = cache_env >= 0 ? cache_env
-                  : (sv.cache_nodes > 0 ? sv.cache_nodes : 64);
-    int n_cached = cache_req < sv.n_nodes4 ? cache_req : sv.n_nodes4;
-    // keep at least 4 LDS stack entries per thread alongside the cache
-    int cache_cap = (20 * 256 * 8 - 4 * 256 * 8) / (int)sizeof(TravNode);
-    if (n_cached > cache_cap) n_cached = cache_cap;
-    static int stack_in_lds = [] {
-        const char* e = getenv("HIPPT_STACK");
-        return (e && strcmp(e, "scratch") == 0) ? 0 : 1;   // default: lds
-    }();
-    const int lds_budget = stack_in_lds
-        ? (occ_v <= 3 ? 26 : occ_v == 4 ? 20 : occ_v == 5 ? 16 : 12) * 256 * 8 : 0;
-    const int lds_n = lds_budget > 0
-        ? (lds_budget - n_cached * (int)sizeof(TravNode)) / (256 * 8) : 0;
-    const uint32_t shmem = (uint32_t)(lds_n * 256 * 8 + n_cached * (int)sizeof(TravNode));
+    static const bool stack_in_lds = !env_is("HIPPT_STACK", "scratch");
+    const LdsPlan plan = lds_plan(occ_v, stack_in_lds, false, sv.n_nodes4,
+                                  (int)sizeof(TravNode), top_cache_request(sv));
+    const int lds_n = plan.lds_n, n_cached = plan.n_cached;
+    const uint32_t shmem = plan.shmem;
     const int w = sv.cam.w, h = sv.cam.h;
     if (y1 <= 0 || y1 > h) y1 = h;
     if (y0 < 0) y0 = 0;
     dim3 block(16, 16);
     dim3 grid((w + 15) / 16, (y1 - y0 + 15) / 16);
+    // every k_render instantiation has this signature: the switch picks one
+    void (*k)(SceneView, float*, float*, int, int, uint32_t, int, int, int, int, int,
+              const uint8_t*, float*) = nullptr;
     switch (renderer) {
     case R_LIGHT_TRACE: {
         long long n_paths = (long long)w * h * nspp;
@@ -261,22 +232,11 @@ int launch_render(const SceneView& sv, float* accum, float* var,
         break;
     }
     case R_VOLUME_PT:
-        if (sv.media_bricks) {
-            if (occ_v == 4)
-                hipLaunchKernelGGL((k_render<R_VOLUME_PT, 4, true>), grid, block, shmem, st, sv, accum, var, spp0, nspp, seed, swiz(), lds_n, n_cached, y0, y1, spp_map, aux);
-            else
-                hipLaunchKernelGGL((k_render<R_VOLUME_PT, 6, true>), grid, block, shmem, st, sv, accum, var, spp0, nspp, seed, swiz(), lds_n, n_cached, y0, y1, spp_map, aux);
-        } else if (occ_v == 4)
-            hipLaunchKernelGGL((k_render<R_VOLUME_PT, 4>), grid, block, shmem, st, sv, accum, var, spp0, nspp, seed, swiz(), lds_n, n_cached, y0, y1, spp_map, aux);
-        else
-            hipLaunchKernelGGL((k_render<R_VOLUME_PT, 6>), grid, block, shmem, st, sv, accum, var, spp0, nspp, seed, swiz(), lds_n, n_cached, y0, y1, spp_map, aux);
+        if (sv.media_bricks) k = occ_v == 4 ? k_render<R_VOLUME_PT, 4, true> : k_render<R_VOLUME_PT, 6, true>;
+        else k = occ_v == 4 ? k_render<R_VOLUME_PT, 4> : k_render<R_VOLUME_PT, 6>;
         break;
-    case R_DEPTH:
-        hipLaunchKernelGGL((k_render<R_DEPTH, 6>), grid, block, shmem, st, sv, accum, var, spp0, nspp, seed, 0, lds_n, n_cached, y0, y1, spp_map, aux);
-        break;
-    case R_BVH_COST:
-        hipLaunchKernelGGL((k_render<R_BVH_COST, 6>), grid, block, shmem, st, sv, accum, var, spp0, nspp, seed, 0, lds_n, n_cached, y0, y1, spp_map, aux);
-        break;
+    case R_DEPTH: k = k_render<R_DEPTH, 6>; break;
+    case R_BVH_COST: k = k_render<R_BVH_COST, 6>; break;
     case R_MEGAKERNEL_PT_DYN: {
         // per-device work counters, freed at process exit (one process may
         // drive several devices: one slot per device id)
@@ -298,20 +258,16 @@ int launch_render(const SceneView& sv, float* accum, float* var,
                            tiles_x * tiles_y, lds_n);
         break;
     }
-    default: {
-        if (occ_v <= 3)
-            hipLaunchKernelGGL((k_render<R_MEGAKERNEL_PT, 3>), grid, block, shmem, st, sv, accum, var, spp0, nspp, seed, swiz(), lds_n, n_cached, y0, y1, spp_map, aux);
-        else if (occ_v == 4)
-            hipLaunchKernelGGL((k_render<R_MEGAKERNEL_PT, 4>), grid, block, shmem, st, sv, accum, var, spp0, nspp, seed, swiz(), lds_n, n_cached, y0, y1, spp_map, aux);
-        else if (occ_v == 5)
-            hipLaunchKernelGGL((k_render<R_MEGAKERNEL_PT, 5>), grid, block, shmem, st, sv, accum, var, spp0, nspp, seed, swiz(), lds_n, n_cached, y0, y1, spp_map, aux);
-        else if (occ_v >= 8)
-            hipLaunchKernelGGL((k_render<R_MEGAKERNEL_PT, 8>), grid, block, shmem, st, sv, accum, var, spp0, nspp, seed, swiz(), lds_n, n_cached, y0, y1, spp_map, aux);
-        else
-            hipLaunchKernelGGL((k_render<R_MEGAKERNEL_PT, 6>), grid, block, shmem, st, sv, accum, var, spp0, nspp, seed, swiz(), lds_n, n_cached, y0, y1, spp_map, aux);
+    default:
+        if (occ_v <= 3) k = k_render<R_MEGAKERNEL_PT, 3>;
+        else if (occ_v == 4) k = k_render<R_MEGAKERNEL_PT, 4>;
+        else if (occ_v == 5) k = k_render<R_MEGAKERNEL_PT, 5>;
+        else if (occ_v >= 8) k = k_render<R_MEGAKERNEL_PT, 8>;
+        else k = k_render<R_MEGAKERNEL_PT, 6>;
         break;
     }
-    }
+    if (k) hipLaunchKernelGGL(k, grid, block, shmem, st, sv, accum, var, spp0, nspp, seed,
+                              swiz, lds_n, n_cached, y0, y1, spp_map, aux);
     return (int)hipGetLastError();
 }
 

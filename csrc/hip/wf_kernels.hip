@@ -35,8 +35,7 @@
 //     shade / shadow-queue / trace per-bounce pipeline for A/B.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
-#include <cstdlib>
-#include <cstring>
+#include "trav_lds.h"
 #include "../core/integrator.h"
 
 namespace hippt {
@@ -75,25 +74,8 @@ __device__ __forceinline__ uint32_t pack_counts(int d, int s, int t, int b) {
     return (uint32_t)(d | (s << 8) | (t << 16) | (b << 24));
 }
 
-// Dynamic-LDS layout for all traversal kernels here, same as the megakernel
-// (pt_kernels.hip k_render): [n_cached 128-byte top-tree nodes][stacks].
-// Every walk's first visits are nodes 0..n_cached and the walk is bound by
-// hit LATENCY (95% L2 hit rate) — LDS is ~4x closer than L2.  Round-1 WFPT
-// omitted this cache; it was the bulk of the megakernel-vs-wavefront gap
-// (trace alone cost as much as the whole megakernel, profiles/README.md r02).
-__device__ __forceinline__ TravCtx wf_lds_ctx(const SceneView& sv, uint64_t* s_stk,
-                                              int lds_n, int n_cached) {
-    constexpr int NW = (int)(sizeof(TravNode) / 8);   // u64 words per node
-    TravNode* s_cache = (TravNode*)s_stk;
-    uint64_t* s_base = s_stk + (size_t)n_cached * NW;
-    for (int i = threadIdx.x; i < n_cached * NW; i += 256)
-        ((uint64_t*)s_cache)[i] = ((const uint64_t*)trav_nodes(sv))[i];
-    if (n_cached > 0) __syncthreads();
-    return TravCtx{(LdsSlot)&s_base[threadIdx.x], lds_n, s_cache, n_cached};
-}
-
 // ----------------------------------------------------------------- raygen
-template <int MINW = 4>
+template <int MINW>
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(MINW, MINW)))  // exact residency = what the
 // LDS stack budget allows; frees 512/MINW VGPRs so the walk state does not
@@ -101,7 +83,7 @@ __attribute__((amdgpu_waves_per_eu(MINW, MINW)))  // exact residency = what the
 void k_wf_raygen(SceneView sv, WfState st, int spp_idx, uint32_t seed, int lds_n,
                  int n_cached) {
     extern __shared__ uint64_t s_stk[];
-    TravCtx tc = wf_lds_ctx(sv, s_stk, lds_n, n_cached);
+    TravCtx tc = trav_lds_ctx(sv, s_stk, threadIdx.x, lds_n, n_cached);
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= st.n) return;
     int px = i % st.w, py = i / st.w;
@@ -357,14 +339,14 @@ void k_wf_shade(SceneView sv, WfState st, const uint32_t* __restrict__ order,
 // ---------------------------------------------------- shadow-ray resolve
 // Lean traversal-only kernel (58 VGPR class -> 8 waves/SIMD): any-hit test,
 // then a race-free add into L (exactly one shadow ray per payload per bounce).
-template <int MINW = 4>
+template <int MINW>
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(MINW, MINW)))  // exact residency = what the
 // LDS stack budget allows; frees 512/MINW VGPRs so the walk state does not
 // spill (same fix as the megakernel, measured +9% there)
 void k_wf_shadow(SceneView sv, WfState st, int lds_n, int n_cached) {
     extern __shared__ uint64_t s_stk[];
-    TravCtx tc = wf_lds_ctx(sv, s_stk, lds_n, n_cached);
+    TravCtx tc = trav_lds_ctx(sv, s_stk, threadIdx.x, lds_n, n_cached);
     int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= *st.sh_cnt) return;
     float4 od = st.sh_od[k];
@@ -418,7 +400,7 @@ __device__ inline void wf_trace_finish(const SceneView& sv, WfState& st, int i,
 // adjacency from the scatter, so wave-level spatial coherence survives the
 // material grouping.  Shade may have terminated a ray after the sort ran,
 // so the fresh status byte is still checked.
-template <int MINW = 4>
+template <int MINW>
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(MINW, MINW)))  // exact residency = what the
 // LDS stack budget allows; frees 512/MINW VGPRs so the walk state does not
@@ -426,7 +408,7 @@ __attribute__((amdgpu_waves_per_eu(MINW, MINW)))  // exact residency = what the
 void k_wf_trace(SceneView sv, WfState st, const uint32_t* __restrict__ order,
                 int live, int lds_n, int n_cached) {
     extern __shared__ uint64_t s_stk[];
-    TravCtx tc = wf_lds_ctx(sv, s_stk, lds_n, n_cached);
+    TravCtx tc = trav_lds_ctx(sv, s_stk, threadIdx.x, lds_n, n_cached);
     int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= live) return;
     int i = (int)(order[k] & 0x00FFFFFFu);
@@ -563,13 +545,13 @@ __device__ __forceinline__ void wf_step_core(const SceneView& sv, WfState& st, i
 // BVH walk shade VALU work to overlap.  The sort/compaction stays — the
 // wavefront's actual value on this hardware.  HIPPT_WF_FUSE=0 restores the
 // split pipeline for A/B.
-template <int MINW = 4>
+template <int MINW>
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(MINW, MINW)))
 void k_wf_step(SceneView sv, WfState st, const uint32_t* __restrict__ order,
                int live, int extra_bounces, int do_trace, int lds_n, int n_cached) {
     extern __shared__ uint64_t s_stk[];
-    TravCtx tc = wf_lds_ctx(sv, s_stk, lds_n, n_cached);
+    TravCtx tc = trav_lds_ctx(sv, s_stk, threadIdx.x, lds_n, n_cached);
     int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= live) return;
     int i = (int)(order[k] & 0x00FFFFFFu);
@@ -585,13 +567,13 @@ void k_wf_step(SceneView sv, WfState st, const uint32_t* __restrict__ order,
 // (replaces the separate raygen: no payload round trip or sort before the
 // first shade — primary rays are pixel-coherent anyway, and the
 // material-grouped shade was measured neutral).
-template <int MINW = 4>
+template <int MINW>
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(MINW, MINW)))
 void k_wf_primary(SceneView sv, WfState st, int spp_idx, uint32_t seed,
                   int extra_bounces, int do_trace, int lds_n, int n_cached) {
     extern __shared__ uint64_t s_stk[];
-    TravCtx tc = wf_lds_ctx(sv, s_stk, lds_n, n_cached);
+    TravCtx tc = trav_lds_ctx(sv, s_stk, threadIdx.x, lds_n, n_cached);
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= st.n) return;
     int px = i % st.w, py = i / st.w;
@@ -613,7 +595,7 @@ void k_wf_primary(SceneView sv, WfState st, int spp_idx, uint32_t seed,
 // then loop full path_step bounces (inline NEE occlusion, no shadow
 // queue) until the path dies.  Mirrors the reference's early loop exit at
 // live == 0 (wf_path_tracer.cu:199-210) taken one step further.
-template <int MINW = 4>
+template <int MINW>
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(MINW, MINW)))  // exact residency = what the
 // LDS stack budget allows; frees 512/MINW VGPRs so the walk state does not
@@ -621,7 +603,7 @@ __attribute__((amdgpu_waves_per_eu(MINW, MINW)))  // exact residency = what the
 void k_wf_tail(SceneView sv, WfState st, const uint32_t* __restrict__ order,
                int live, int lds_n, int n_cached) {
     extern __shared__ uint64_t s_stk[];
-    TravCtx tc = wf_lds_ctx(sv, s_stk, lds_n, n_cached);
+    TravCtx tc = trav_lds_ctx(sv, s_stk, threadIdx.x, lds_n, n_cached);
     int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= live) return;
     int i = (int)(order[k] & 0x00FFFFFFu);
@@ -702,121 +684,62 @@ void wf_destroy(WfState* s) {
 // HIPPT_WF_OCC = exact waves/SIMD for the traversal kernels (both the
 // amdgpu_waves_per_eu instantiation — frees 512/occ VGPRs so the walk
 // state does not spill — AND the matching LDS block budget).  Default 4,
-// the megakernel's measured best.
+// the megakernel's measured best (span>=4 ladder: occ4 143-146 vs occ3 136).
 static int wf_occ() {
-    static int occ_v = [] {
-        const char* e = getenv("HIPPT_WF_OCC");
-        int occ = e ? atoi(e) : 4;   // span>=4 ladder: occ4 143-146 vs occ3 136
-        return occ < 3 ? 3 : (occ > 6 ? 6 : occ);
-    }();
-    return occ_v;
+    static const int occ = env_int("HIPPT_WF_OCC", 4);
+    return occ < 3 ? 3 : (occ > 6 ? 6 : occ);
 }
+// the instantiation of traversal kernel template `k` that wf_occ() selects
+#define WF_BY_OCC(k) (wf_occ() == 3 ? k<3> : wf_occ() == 4 ? k<4> : wf_occ() == 5 ? k<5> : k<6>)
 
-// Dynamic-LDS plan of every traversal kernel here (see wf_lds_ctx): the
-// block budget follows the occupancy, the top-tree cache takes its share
-// first and the stacks get the rest.  HIPPT_WF_STACK=scratch disables the
-// LDS stack + cache entirely (A/B hook).  lds_req / cache_in >= 0 replace
-// the launcher's own choice (ray probe) and pass through the same clamps.
-struct WfLdsPlan { int lds_n, n_cached; uint32_t shmem; };
-static WfLdsPlan wf_lds_plan(const SceneView& sv, int lds_req = -1, int cache_in = -1) {
-    const int occ_v = wf_occ();
-    static int lds_budget = [occ_v] {
-        const char* e = getenv("HIPPT_WF_STACK");
-        if (e && strcmp(e, "scratch") == 0) return 0;
-        return (occ_v == 3 ? 26 : occ_v == 4 ? 20 : occ_v == 5 ? 16 : 12) * WF_BLOCK * 8;
-    }();
-    // LDS top-tree cache shares the block budget with the stacks (same
-    // occupancy, fewer LDS stack entries; overflow spills to scratch)
-    static int cache_env = [] {
-        const char* e = getenv("HIPPT_TOPCACHE");
-        return e ? atoi(e) : -1;
-    }();
-    int cache_req = cache_in >= 0 ? (cache_in < sv.n_nodes4 ? cache_in : sv.n_nodes4)
-                  : cache_env >= 0 ? cache_env
-                  : (sv.cache_nodes > 0 ? sv.cache_nodes : 64);
-    if (cache_req * (int)sizeof(TravNode) > lds_budget - 4 * WF_BLOCK * 8)
-        cache_req = (lds_budget - 4 * WF_BLOCK * 8) / (int)sizeof(TravNode);
-    WfLdsPlan p;
-    p.n_cached = lds_budget > 0
-        ? (cache_req < sv.n_nodes4 ? cache_req : sv.n_nodes4) : 0;
-    const int lds_max = lds_budget > 0
-        ? (lds_budget - p.n_cached * (int)sizeof(TravNode)) / (WF_BLOCK * 8) : 0;
-    p.lds_n = lds_req >= 0 && lds_req < lds_max ? lds_req : lds_max;
-    p.shmem = (uint32_t)(p.lds_n * WF_BLOCK * 8 + p.n_cached * (int)sizeof(TravNode));
-    return p;
+// Dynamic-LDS plan of every traversal kernel here (lds_plan.h).
+// HIPPT_WF_STACK=scratch disables the LDS stack + cache entirely (A/B hook).
+// lds_req / cache_in >= 0 replace the launcher's own choice (ray probe) and
+// pass through the same clamps.
+static LdsPlan wf_lds_plan(const SceneView& sv, int lds_req = -1, int cache_in = -1) {
+    static const bool stack_in_lds = !env_is("HIPPT_WF_STACK", "scratch");
+    return lds_plan(wf_occ(), stack_in_lds, true, sv.n_nodes4, (int)sizeof(TravNode),
+                    top_cache_request(sv, cache_in), lds_req);
 }
 
 int launch_render_wavefront(WfState* st, const SceneView& sv, float* accum, float* var,
                             int spp0, int nspp, uint32_t seed, int sort_mode, void* stream) {
     if (sort_mode < 0 || sort_mode > 1) sort_mode = 0;
-    static int env_mode = [] {
-        const char* e = getenv("HIPPT_WF_SORT");
-        return (e && strcmp(e, "compact") == 0) ? 1 : -1;
-    }();
+    static const int env_mode = env_is("HIPPT_WF_SORT", "compact") ? 1 : -1;
     if (env_mode >= 0) sort_mode = env_mode;
     hipStream_t hs = (hipStream_t)stream;
     const int n = st->n;
     dim3 blk(WF_BLOCK);
     dim3 grd_n((n + WF_BLOCK - 1) / WF_BLOCK);
-    static const int occ_v = wf_occ();
-    using RaygenFn = void (*)(SceneView, WfState, int, uint32_t, int, int);
-    using PrimaryFn = void (*)(SceneView, WfState, int, uint32_t, int, int, int, int);
-    using TraceFn = void (*)(SceneView, WfState, const uint32_t*, int, int, int);
-    using ShadowFn = void (*)(SceneView, WfState, int, int);
-    static RaygenFn f_raygen = occ_v == 3 ? k_wf_raygen<3> : occ_v == 4 ? k_wf_raygen<4>
-                             : occ_v == 5 ? k_wf_raygen<5> : k_wf_raygen<6>;
-    static PrimaryFn f_primary = occ_v == 3 ? k_wf_primary<3> : occ_v == 4 ? k_wf_primary<4>
-                               : occ_v == 5 ? k_wf_primary<5> : k_wf_primary<6>;
-    static int prim_fuse = [] {
-        const char* e = getenv("HIPPT_WF_PRIMARY_FUSE");
-        return e ? atoi(e) : 1;
-    }();
-    static TraceFn f_trace = occ_v == 3 ? k_wf_trace<3> : occ_v == 4 ? k_wf_trace<4>
-                           : occ_v == 5 ? k_wf_trace<5> : k_wf_trace<6>;
-    static TraceFn f_tail = occ_v == 3 ? k_wf_tail<3> : occ_v == 4 ? k_wf_tail<4>
-                          : occ_v == 5 ? k_wf_tail<5> : k_wf_tail<6>;
-    using StepFn = void (*)(SceneView, WfState, const uint32_t*, int, int, int, int, int);
-    static StepFn f_step = occ_v == 3 ? k_wf_step<3> : occ_v == 4 ? k_wf_step<4>
-                         : occ_v == 5 ? k_wf_step<5> : k_wf_step<6>;
-    static int wf_fuse = [] {
-        const char* e = getenv("HIPPT_WF_FUSE");
-        return e ? atoi(e) : 1;
-    }();
-    static int wf_span = [] {
-        // Shades per fused launch between sorts/compactions.  The kitchen
-        // live-count curve (~99% live through bounce 6) makes long spans
-        // pay: measured span1 124.5, span4 142.4, span8 145.9 Msps at occ4
-        // — the optimal sort/compaction cadence on this latency-bound
-        // hardware is about once per 8 bounces.  span=1 restores the
-        // classic per-bounce wavefront.
-        const char* e = getenv("HIPPT_WF_SPAN");
-        int v = e ? atoi(e) : 8;
-        return v < 1 ? 1 : (v > 16 ? 16 : v);
-    }();
-    static ShadowFn f_shadow = occ_v == 3 ? k_wf_shadow<3> : occ_v == 4 ? k_wf_shadow<4>
-                             : occ_v == 5 ? k_wf_shadow<5> : k_wf_shadow<6>;
-    const WfLdsPlan plan = wf_lds_plan(sv);
+    static const auto f_raygen = WF_BY_OCC(k_wf_raygen);
+    static const auto f_primary = WF_BY_OCC(k_wf_primary);
+    static const auto f_trace = WF_BY_OCC(k_wf_trace);
+    static const auto f_tail = WF_BY_OCC(k_wf_tail);
+    static const auto f_step = WF_BY_OCC(k_wf_step);
+    static const auto f_shadow = WF_BY_OCC(k_wf_shadow);
+    static const int prim_fuse = env_int("HIPPT_WF_PRIMARY_FUSE", 1);
+    static const int wf_fuse = env_int("HIPPT_WF_FUSE", 1);
+    // Shades per fused launch between sorts/compactions.  The kitchen
+    // live-count curve (~99% live through bounce 6) makes long spans pay:
+    // measured span1 124.5, span4 142.4, span8 145.9 Msps at occ4 — the
+    // optimal sort/compaction cadence on this latency-bound hardware is
+    // about once per 8 bounces.  span=1 restores the classic per-bounce
+    // wavefront.
+    static const int span_env = env_int("HIPPT_WF_SPAN", 8);
+    static const int wf_span = span_env < 1 ? 1 : (span_env > 16 ? 16 : span_env);
+    const LdsPlan plan = wf_lds_plan(sv);
     const int n_cached = plan.n_cached;
     const int lds_n = plan.lds_n;
     const uint32_t shmem = plan.shmem;
-    static int wf_dual = [] {
-        const char* e = getenv("HIPPT_WF_DUAL");
-        return e ? atoi(e) : 0;
-    }();
+    static int wf_dual = env_int("HIPPT_WF_DUAL", 0);
     // dual-walk stack safety (each walk: BVH4_STACK/2 private + lds_n/2 LDS
     // entries; a node visit pushes at most 3 entries per level)
     if (wf_dual && 3 * sv.bvh4_depth > BVH4_STACK / 2 + lds_n / 2) wf_dual = 0;
-    static int tail_thresh = [] {
-        // Hand off to the fused tail once <=1.5M rays are live (measured
-        // best on kitchen 1080p: per-bounce pipeline overhead outweighs the
-        // wave64 divergence it avoids well before the chip runs dry).
-        const char* e = getenv("HIPPT_WF_TAIL");
-        return e ? atoi(e) : 1500 * 1024;
-    }();
-    static int wf_log = [] {
-        const char* e = getenv("HIPPT_WF_LOG");
-        return e ? atoi(e) : 0;
-    }();
+    // Hand off to the fused tail once <=1.5M rays are live (measured best
+    // on kitchen 1080p: per-bounce pipeline overhead outweighs the wave64
+    // divergence it avoids well before the chip runs dry).
+    static const int tail_thresh = env_int("HIPPT_WF_TAIL", 1500 * 1024);
+    static const int wf_log = env_int("HIPPT_WF_LOG", 0);
     for (int s = 0; s < nspp; ++s) {
         int bounce0;
         const int n_stage = sv.md.max_depth + 1;   // total shades per path
@@ -940,7 +863,7 @@ void k_wf_ray_probe(SceneView sv, const float4* __restrict__ ray_o,
                     float4* __restrict__ hit_out, int* __restrict__ occ_out,
                     int lds_n, int n_cached) {
     extern __shared__ uint64_t s_stk[];
-    TravCtx tc = wf_lds_ctx(sv, s_stk, lds_n, n_cached);
+    TravCtx tc = trav_lds_ctx(sv, s_stk, threadIdx.x, lds_n, n_cached);
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float4 o4 = ray_o[i], d4 = ray_d[i];   // o.w = tmax
@@ -954,7 +877,7 @@ int wf_trace_probe(const SceneView& sv, const float* ray_o_tmax, const float* ra
                    int n, int lds_n, int n_cached, float* hit_out, int* occ_out,
                    int* plan_out) {
     if (n <= 0 || sv.n_nodes4 <= 0) return (int)hipErrorInvalidValue;
-    const WfLdsPlan plan = wf_lds_plan(sv, lds_n, n_cached);
+    const LdsPlan plan = wf_lds_plan(sv, lds_n, n_cached);
     plan_out[0] = plan.lds_n;
     plan_out[1] = plan.n_cached;
     DevBuf<float4> d_o, d_d, d_hit;

@@ -7,7 +7,8 @@ budget, i.e. how many stack entries sit in LDS and how many in private
 memory; it must not change a single bit of the image.  The knob is read at
 the first launch, so every value renders in a process of its own
 (tests/occ_worker.py), each under its own timeout; after the first worker
-that exits non-zero no further one is started.
+that exits non-zero no further one is started.  One more worker asks for a
+top-tree cache larger than its occupancy's LDS budget holds.
 """
 import os
 import subprocess
@@ -39,12 +40,13 @@ def test_device_walks_five_triangles(lds_n, n_cached):
         assert used_lds >= 4 and used_cache == 2     # the whole two-node tree
 
 
-_images = {}          # (renderer, occ) -> accum array
+_images = {}          # (renderer, occ, extra env) -> accum array
 _worker_failed = []   # first failing worker, if any
 
 
-def render_at(tmp_path, renderer, spp, occ):
-    key = (renderer, occ)
+def render_at(tmp_path, renderer, spp, occ, extra_env=None):
+    extra_env = extra_env or {}
+    key = (renderer, occ, tuple(sorted(extra_env.items())))
     if key in _images:
         return _images[key]
     if _worker_failed:
@@ -52,7 +54,8 @@ def render_at(tmp_path, renderer, spp, occ):
     env = {k: v for k, v in os.environ.items() if k != "HIPPT_OCC"}
     if occ is not None:
         env["HIPPT_OCC"] = str(occ)
-    out = str(tmp_path / f"{renderer}_{occ}.npy")
+    env.update(extra_env)
+    out = str(tmp_path / f"{renderer}_{occ}_{len(_images)}.npy")
     try:
         p = subprocess.run([sys.executable, WORKER, renderer, str(spp), out],
                            capture_output=True, text=True, timeout=90, env=env, cwd=ROOT)
@@ -66,9 +69,9 @@ def render_at(tmp_path, renderer, spp, occ):
     return _images[key]
 
 
-def check_same_image(tmp_path, renderer, spp, occ):
+def check_same_image(tmp_path, renderer, spp, occ, extra_env=None):
     ref = render_at(tmp_path, renderer, spp, None)
-    img = render_at(tmp_path, renderer, spp, occ)
+    img = render_at(tmp_path, renderer, spp, occ, extra_env)
     assert ref.shape == (36, 64, 4) and np.isfinite(ref).all()
     assert float(ref[..., :3].mean()) > 1e-3 and (ref[..., 3] == spp).all()
     np.testing.assert_array_equal(img, ref)
@@ -82,3 +85,9 @@ def test_pt_image_same_at_every_occupancy(tmp_path, occ):
 @pytest.mark.parametrize("occ", [4, 6])
 def test_vpt_image_same_at_every_occupancy(tmp_path, occ):
     check_same_image(tmp_path, "vpt", 2, occ)
+
+
+def test_pt_image_same_with_cache_request_above_the_budget(tmp_path):
+    # 256 nodes do not fit beside 4 stack entries in the 12-entry budget of
+    # occupancy 6: the plan cuts the cache to 128 (tests/test_lds_plan.py)
+    check_same_image(tmp_path, "pt", 4, 6, {"HIPPT_TOPCACHE": "256"})
