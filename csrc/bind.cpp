@@ -91,6 +91,20 @@ int bvh4_tree_depth(const BVH4Node* nodes, int n) {
 
 static std::vector<uint64_t> host_lds_slots(int lds_n);   // below, with the self-tests
 
+// Per-primitive shade words (shade_load.h) from prim_obj and the (n,8) object
+// table; throws when a bsdf or emitter id does not fit its field.
+std::vector<uint32_t> make_prim_shade(const uint32_t* prim_obj, size_t n_prims,
+                                      const int32_t* objs, size_t n_objs) {
+    std::vector<uint32_t> out(n_prims);
+    int bad = -1;
+    if (!build_prim_shade(prim_obj, (int)n_prims, objs, (int)n_objs, out.data(), &bad))
+        throw std::runtime_error(
+            "build_prim_shade: primitive " + std::to_string(bad) +
+            " needs object < n_objs, 0 <= bsdf_id < " + std::to_string(SHADE_MAX_BSDFS) +
+            " and emitter_id < " + std::to_string(SHADE_MAX_EMITTERS));
+    return out;
+}
+
 struct SceneHolder {
     // ----- host data (kept alive / owned)
     farr np_prims, np_attrs, np_nodes, np_nodes4, np_nodes8;
@@ -108,6 +122,9 @@ struct SceneHolder {
     std::vector<TexView> tex_host;
     std::vector<int> emitter_prims;
     std::vector<float> emitter_cdf;
+    std::vector<uint32_t> prim_shade;         // rebuilt by finalize() when stale
+    std::vector<LightPrim> light_prims;       // likewise (emitter.h)
+    bool shade_stale = true;
     std::vector<float> env_rows_h, env_cols_h;
     int env_w = 0, env_h = 0;
     std::vector<float> emitter_sel_h;
@@ -150,6 +167,7 @@ struct SceneHolder {
         np_prims = std::move(prims);
         np_attrs = std::move(attrs);
         np_prim_obj = std::move(prim_obj);
+        shade_stale = true;
         np_nodes = std::move(nodes);
         np_nodes4 = std::move(nodes4);
         if (nodes8.ndim() == 2 && nodes8.shape(0) > 0 && nodes8.shape(1) != 64)
@@ -206,6 +224,7 @@ struct SceneHolder {
     void set_objects(iarr objs) {
         if (objs.ndim() != 2 || objs.shape(1) != 8) throw std::runtime_error("objs must be (n,8)");
         np_objs = std::move(objs);
+        shade_stale = true;
     }
 
     int add_bsdf(int type, std::vector<float> kd, std::vector<float> ks, std::vector<float> kg,
@@ -258,6 +277,7 @@ struct SceneHolder {
 
     void set_emitter_prims(iarr eprims, farr ecdf) {
         emitter_prims.assign(eprims.data(), eprims.data() + eprims.size());
+        shade_stale = true;
         emitter_cdf.assign(ecdf.data(), ecdf.data() + ecdf.size());
     }
 
@@ -579,6 +599,20 @@ struct SceneHolder {
     }
 
     void finalize() {
+        if (shade_stale) {
+            prim_shade = make_prim_shade(np_prim_obj.data(), (size_t)np_prim_obj.size(),
+                                         np_objs.data(),
+                                         np_objs.ndim() == 2 ? (size_t)np_objs.shape(0) : 0);
+            const int n_prims = np_prims.ndim() == 2 ? (int)np_prims.shape(0) : 0;
+            for (int pid : emitter_prims)
+                if (pid < 0 || pid >= n_prims)
+                    throw std::runtime_error("emitter_prims entry outside the primitive array");
+            light_prims.resize(emitter_prims.size());
+            build_light_prims((const Prim*)np_prims.data(), (const PrimAttr*)np_attrs.data(),
+                              np_prim_obj.data(), emitter_prims.data(), emitter_prims.size(),
+                              light_prims.data());
+            shade_stale = false;
+        }
         fill_common(host_sv);
         host_sv.nodes = (const BVHNode*)np_nodes.data();
         host_sv.nodes4 = host_sv.n_nodes4 > 0 ? (const BVH4Node*)np_nodes4.data() : nullptr;
@@ -589,10 +623,12 @@ struct SceneHolder {
         host_sv.attrs = (const PrimAttr*)np_attrs.data();
         host_sv.prim_obj = np_prim_obj.data();
         host_sv.objs = (const ObjInfo*)np_objs.data();
+        host_sv.prim_shade = prim_shade.data();
         host_sv.bsdfs = bsdfs.data();
         host_sv.emitters = emitters.data();
         host_sv.emitter_prims = emitter_prims.data();
         host_sv.emitter_cdf = emitter_cdf.data();
+        host_sv.light_prims = light_prims.data();
         host_sv.env_rows = env_rows_h.empty() ? nullptr : env_rows_h.data();
         host_sv.env_cols = env_cols_h.empty() ? nullptr : env_cols_h.data();
         host_sv.emitter_sel_cdf = emitter_sel_h.empty() ? nullptr : emitter_sel_h.data();
@@ -630,8 +666,10 @@ struct SceneHolder {
         dev_sv.attrs = upload_vec((const PrimAttr*)np_attrs.data(), np_attrs.shape(0));
         dev_sv.prim_obj = upload_vec(np_prim_obj.data(), np_prim_obj.size());
         dev_sv.objs = upload_vec((const ObjInfo*)np_objs.data(), np_objs.shape(0));
+        dev_sv.prim_shade = upload_vec(prim_shade.data(), prim_shade.size());
         dev_sv.emitter_prims = upload_vec(emitter_prims.data(), emitter_prims.size());
         dev_sv.emitter_cdf = upload_vec(emitter_cdf.data(), emitter_cdf.size());
+        dev_sv.light_prims = upload_vec(light_prims.data(), light_prims.size());
         dev_sv.env_rows = upload_vec(env_rows_h.data(), env_rows_h.size());
         dev_sv.env_cols = upload_vec(env_cols_h.data(), env_cols_h.size());
         dev_sv.emitter_sel_cdf = upload_vec(emitter_sel_h.data(), emitter_sel_h.size());
@@ -786,6 +824,61 @@ struct SceneHolder {
         }
         return py::make_tuple(t_out, p_out, u_out, v_out, occ_out,
                               py::make_tuple(plan[0], plan[1]));
+    }
+
+    // The records a hit on each of prim_idx gathers, through the loaders the
+    // shaders use (core/shade_load.h): on host_sv (device < 0) or on the
+    // uploaded scene.  Returns (attr (n,16), word (n,), bsdf (n,20),
+    // emitter (n,16)) as uint32.
+    py::tuple shade_probe_py(iarr prim_idx, int device) {
+        const int n = (int)prim_idx.size();
+        finalize();
+        const int n_prims = host_sv.n_prims;
+        for (int i = 0; i < n; ++i)
+            if (prim_idx.data()[i] < 0 || prim_idx.data()[i] >= n_prims)
+                throw std::runtime_error("shade_probe: primitive index out of range");
+        std::vector<uint32_t> raw((size_t)n * SHADE_PROBE_WORDS, 0u);
+        if (n > 0) {
+            if (device < 0) {
+                for (int i = 0; i < n; ++i)
+                    shade_probe_record(host_sv, prim_idx.data()[i],
+                                       raw.data() + (size_t)i * SHADE_PROBE_WORDS);
+            } else {
+                if (!has_dev) throw std::runtime_error("scene not uploaded to device");
+                HIP_OK(shade_probe(dev_sv, prim_idx.data(), n, raw.data()));
+            }
+        }
+        uarr attr({n, 16}), word(n), bsdf({n, 20}), em({n, 16});
+        for (int i = 0; i < n; ++i) {
+            const uint32_t* r = raw.data() + (size_t)i * SHADE_PROBE_WORDS;
+            std::memcpy(attr.mutable_data() + (size_t)i * 16, r, 64);
+            word.mutable_data()[i] = r[16];
+            std::memcpy(bsdf.mutable_data() + (size_t)i * 20, r + 17, 80);
+            std::memcpy(em.mutable_data() + (size_t)i * 16, r + 37, 64);
+        }
+        return py::make_tuple(attr, word, bsdf, em);
+    }
+
+    // Test hook (tests/test_shade_tables.py, tests/shade_util.py), not part of
+    // the rendering API: the host tables behind the shading loaders, as raw
+    // uint32 copies: bsdfs (n,20), emitters (n,16), prim_shade (n,),
+    // light_prims (n,32).
+    py::dict tables() {
+        finalize();
+        auto rows = [](const void* src, size_t n, int words) {
+            uarr a({(py::ssize_t)n, (py::ssize_t)words});
+            if (n) std::memcpy(a.mutable_data(), src, n * words * 4);
+            return a;
+        };
+        py::dict d;
+        d["bsdfs"] = rows(bsdfs.data(), bsdfs.size(), sizeof(BsdfParams) / 4);
+        d["emitters"] = rows(emitters.data(), emitters.size(), sizeof(EmitterParams) / 4);
+        d["light_prims"] = rows(light_prims.data(), light_prims.size(), sizeof(LightPrim) / 4);
+        uarr w((py::ssize_t)prim_shade.size());
+        if (!prim_shade.empty())
+            std::memcpy(w.mutable_data(), prim_shade.data(), prim_shade.size() * 4);
+        d["prim_shade"] = w;
+        return d;
     }
 
     py::dict info() {
@@ -1209,6 +1302,9 @@ PYBIND11_MODULE(_C, m) {
         .def("trace_rays", &SceneHolder::trace_rays, py::arg("o"), py::arg("d"),
              py::arg("tmax"), py::arg("device"), py::arg("lds_n") = -1,
              py::arg("n_cached") = -1)
+        .def("shade_probe", &SceneHolder::shade_probe_py, py::arg("prim_idx"),
+             py::arg("device"))
+        .def("tables", &SceneHolder::tables)
         .def("info", &SceneHolder::info);
 
     m.def("build_bvh", &py_build_bvh, py::arg("prims"), py::arg("prim_obj"),
@@ -1223,6 +1319,30 @@ PYBIND11_MODULE(_C, m) {
           py::arg("ray_o"), py::arg("ray_d"), py::arg("tmax"));
     m.def("bvh4_any_visit_selftest", &py_bvh4_any_visit_selftest, py::arg("nodes4"),
           py::arg("ray_o"), py::arg("ray_d"), py::arg("tmax"));
+    m.def("build_prim_shade", [](uarr prim_obj, iarr objs) {
+        if (objs.ndim() != 2 || objs.shape(1) != 8) throw std::runtime_error("objs must be (n,8)");
+        std::vector<uint32_t> w = make_prim_shade(prim_obj.data(), (size_t)prim_obj.size(),
+                                                  objs.data(), (size_t)objs.shape(0));
+        uarr out((py::ssize_t)w.size());
+        if (!w.empty()) std::memcpy(out.mutable_data(), w.data(), w.size() * 4);
+        return out;
+    }, py::arg("prim_obj"), py::arg("objs"));
+    m.def("build_light_prims", [](farr prims, farr attrs, uarr prim_obj, iarr emitter_prims) {
+        if (prims.ndim() != 2 || prims.shape(1) != 12) throw std::runtime_error("prims must be (n,12)");
+        if (attrs.ndim() != 2 || attrs.shape(1) != 16) throw std::runtime_error("attrs must be (n,16)");
+        const py::ssize_t n_prims = prims.shape(0);
+        if (attrs.shape(0) != n_prims || prim_obj.size() != n_prims)
+            throw std::runtime_error("prims, attrs and prim_obj must have one row per primitive");
+        const py::ssize_t n = emitter_prims.size();
+        for (py::ssize_t k = 0; k < n; ++k)
+            if (emitter_prims.data()[k] < 0 || emitter_prims.data()[k] >= n_prims)
+                throw std::runtime_error("emitter_prims entry outside the primitive array");
+        uarr out({n, (py::ssize_t)32});
+        build_light_prims((const Prim*)prims.data(), (const PrimAttr*)attrs.data(),
+                          prim_obj.data(), emitter_prims.data(), (size_t)n,
+                          (LightPrim*)out.mutable_data());
+        return out;
+    }, py::arg("prims"), py::arg("attrs"), py::arg("prim_obj"), py::arg("emitter_prims"));
     m.def("bsdf_check", &py_bsdf_check);
     m.def("env_check", &py_env_check);
     m.def("bvh4q_selftest", &py_bvh4q_selftest,

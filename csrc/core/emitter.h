@@ -44,12 +44,51 @@ struct EmitterSampleRec {
     bool delta;
 };
 
+// One light primitive as NEE reads it: exact copies of the Prim, its
+// PrimAttr and its sphere flag, one 128-byte record per entry of
+// emitter_prims and in the same order.  Sampling a light primitive was
+// emitter_prims[k] -> {prims, prim_obj, attrs}[pid], two dependent hops with
+// the three tables behind separate waits; the record at prim_base + k is one
+// gather.  Built on the host (build_light_prims).
+struct alignas(16) LightPrim {
+    Prim prim;
+    PrimAttr attr;
+    uint32_t sphere;   // prim_obj & PRIM_SPHERE_BIT
+    uint32_t pad[3];
+};
+static_assert(sizeof(LightPrim) == 128, "LightPrim is one 128-byte record");
+
+inline void build_light_prims(const Prim* prims, const PrimAttr* attrs,
+                              const uint32_t* prim_obj, const int32_t* emitter_prims,
+                              size_t n, LightPrim* out) {
+    for (size_t k = 0; k < n; ++k) {
+        const int32_t pid = emitter_prims[k];
+        LightPrim& lp = out[k];
+        lp.prim = prims[pid];
+        lp.attr = attrs[pid];
+        lp.sphere = prim_obj[pid] & PRIM_SPHERE_BIT;
+        lp.pad[0] = lp.pad[1] = lp.pad[2] = 0u;
+    }
+}
+
+// The whole record behind one wait (the loader pattern of shade_load.h; the
+// host hands out the table entry itself, see there).
+#if !HIPPT_ON_DEVICE
+HD const LightPrim& load_light_prim(const LightPrim* light_prims, int k) { return light_prims[k]; }
+#else
+HD LightPrim load_light_prim(const LightPrim* light_prims, int k) {
+    const LightPrim lp = light_prims[k];
+    asm volatile("" :: HIPPT_LANDED_VEC4(lp.prim.v0), HIPPT_LANDED_VEC4(lp.prim.e1),
+                       HIPPT_LANDED_VEC4(lp.prim.e2), HIPPT_LANDED_VEC4(lp.attr.n0),
+                       HIPPT_LANDED_VEC4(lp.attr.n1), HIPPT_LANDED_VEC4(lp.attr.n2),
+                       HIPPT_LANDED_VEC4(lp.attr.uvrest), "v"(lp.sphere));
+    return lp;
+}
+#endif
+
 // geometry arrays needed to sample area lights
 struct EmitterGeom {
-    const Prim* prims;
-    const PrimAttr* attrs;
-    const uint32_t* prim_obj;
-    const int* emitter_prims;     // BVH-reordered primitive ids per emitter
+    const LightPrim* light_prims; // per entry of emitter_prims: prim + attrs + sphere flag
     const float* emitter_cdf;     // per-emitter cumulative areas, normalized [0,1]
     const TexView* textures;
     // envmap importance sampling (beyond reference: the reference only does
@@ -158,9 +197,9 @@ HD EmitterSampleRec emitter_sample(const EmitterParams& e, const EmitterGeom& g,
         const float* cdf = g.emitter_cdf + e.prim_base;
         int lo = 0, hi = cnt - 1;
         while (lo < hi) { int mid = (lo + hi) >> 1; if (cdf[mid] < xi) lo = mid + 1; else hi = mid; }
-        int pid = g.emitter_prims[e.prim_base + lo];
-        const Prim p = g.prims[pid];
-        bool sph = (g.prim_obj[pid] & PRIM_SPHERE_BIT) != 0;
+        const auto& lp = load_light_prim(g.light_prims, e.prim_base + lo);
+        const Prim p = lp.prim;
+        bool sph = lp.sphere != 0;
         Vec3 lpos, ln; Vec2 uv{0.f, 0.f};
         if (sph) {
             float pdf_dir;
@@ -170,7 +209,7 @@ HD EmitterSampleRec emitter_sample(const EmitterParams& e, const EmitterGeom& g,
         } else {
             Vec3 bc = sample_triangle_bary(sampler.next2f());
             lpos = p.v0.xyz() + p.e1.xyz() * bc.y + p.e2.xyz() * bc.z;
-            const PrimAttr a = g.attrs[pid];
+            const PrimAttr a = lp.attr;
             Vec3 nsum = a.n0.xyz() * bc.x + a.n1.xyz() * bc.y + a.n2.xyz() * bc.z;
             ln = nsum.length2() > 1e-16f ? nsum.normalized()
                                          : p.e1.xyz().cross(p.e2.xyz()).normalized();
@@ -288,9 +327,9 @@ HD EmitterLeRec emitter_sample_le(const EmitterParams& e, const EmitterGeom& g, 
         const float* cdf = g.emitter_cdf + e.prim_base;
         int lo = 0, hi = cnt - 1;
         while (lo < hi) { int mid = (lo + hi) >> 1; if (cdf[mid] < xi) lo = mid + 1; else hi = mid; }
-        int pid = g.emitter_prims[e.prim_base + lo];
-        const Prim p = g.prims[pid];
-        bool sph = (g.prim_obj[pid] & PRIM_SPHERE_BIT) != 0;
+        const auto& lp = load_light_prim(g.light_prims, e.prim_base + lo);
+        const Prim p = lp.prim;
+        bool sph = lp.sphere != 0;
         Vec3 lpos, ln; Vec2 uv{0.f, 0.f};
         if (sph) {
             float pdf_sph;
@@ -300,7 +339,7 @@ HD EmitterLeRec emitter_sample_le(const EmitterParams& e, const EmitterGeom& g, 
         } else {
             Vec3 bc = sample_triangle_bary(sampler.next2f());
             lpos = p.v0.xyz() + p.e1.xyz() * bc.y + p.e2.xyz() * bc.z;
-            const PrimAttr a = g.attrs[pid];
+            const PrimAttr a = lp.attr;
             Vec3 nsum = a.n0.xyz() * bc.x + a.n1.xyz() * bc.y + a.n2.xyz() * bc.z;
             ln = nsum.length2() > 1e-16f ? nsum.normalized()
                                          : p.e1.xyz().cross(p.e2.xyz()).normalized();

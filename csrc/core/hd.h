@@ -28,6 +28,14 @@
 #define HIPPT_ON_DEVICE 0
 #endif
 
+// The four components of a Vec4 as "v" inputs of an empty asm statement: the
+// whole-record loaders (bvh4.h bvh_load_prim, emitter.h load_light_prim,
+// shade_load.h) name every loaded dword this way so that a record's loads are
+// issued together and land behind one wait.  Device code only.
+#if HIPPT_ON_DEVICE
+#define HIPPT_LANDED_VEC4(a) "v"((a).x), "v"((a).y), "v"((a).z), "v"((a).w)
+#endif
+
 namespace hippt {
 
 constexpr float EPSILON      = 1e-3f;   // shadow/offset epsilon (reference src/core/constants.cuh)

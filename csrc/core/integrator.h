@@ -106,12 +106,15 @@ HD bool path_shade_hit(const SceneView& sv, PathState& ps, Sampler& sp, TravCtx 
         }
         Vec3 pos = ray.at(hit.t);
         path_time += hit.t;
-        uint32_t po = sv.prim_obj[hit.prim_idx];
-        bool is_sphere = (po & PRIM_SPHERE_BIT) != 0;
-        const ObjInfo& obj = sv.objs[po & PRIM_OBJ_MASK];
-        const Prim prim = sv.prims[hit.prim_idx];
-        Interaction it = get_interaction(prim, sv.attrs[hit.prim_idx], is_sphere, pos, hit.u, hit.v);
-        const BsdfParams& bsdf = sv.bsdfs[obj.bsdf_id];
+        // group 1: attributes + shade word; group 2: the BSDF record whole
+        // (shade_load.h).  The Prim stays lazy: only spheres and degenerate
+        // normals read it.
+        const HitShade hs = load_hit_shade(sv, hit.prim_idx);
+        const bool is_sphere = shade_is_sphere(hs.word);
+        const int bsdf_id = shade_bsdf_id(hs.word);
+        const int emitter_id = shade_emitter_id(hs.word);
+        const auto& bsdf = load_bsdf(sv.bsdfs, bsdf_id);
+        Interaction it = get_interaction(sv.prims[hit.prim_idx], hs.attr, is_sphere, pos, hit.u, hit.v);
         if (bsdf.tex[TEX_NORMAL] >= 0)
             it.shading_n = apply_normal_map(sv.textures, bsdf.tex[TEX_NORMAL], it.uv, it.shading_n);
         if (ps.iter == 1) {
@@ -121,14 +124,14 @@ HD bool path_shade_hit(const SceneView& sv, PathState& ps, Sampler& sp, TravCtx 
         }
 
         // ---- emitter hit accumulation with MIS (megakernel_pt.cu:91-152)
-        if (obj.emitter_id >= 0) {
-            const EmitterParams& em = sv.emitters[obj.emitter_id];
+        if (emitter_id >= 0) {
+            const auto& em = load_emitter(sv.emitters, emitter_id);
             Vec3 le = emitter_eval_le(em, it.shading_n, -ray.d, it.uv, sv.textures);
             if (!le.is_zero()) {
                 float w = 1.f;
                 if (!prev_delta) {
                     float light_pdf = emitter_pdf_hit(em, ray.d, hit.t, it.shading_n, prev_n, sv.emitter_geom()) *
-                                   emitter_sel_pdf(sv, obj.emitter_id);
+                                   emitter_sel_pdf(sv, emitter_id);
                     w = mis_weight(prev_pdf, light_pdf);
                 }
                 if (tof_in_range(sv.md, path_time)) L += thp * le * w;
@@ -137,9 +140,10 @@ HD bool path_shade_hit(const SceneView& sv, PathState& ps, Sampler& sp, TravCtx 
 
         // ---- next-event estimation (one emitter sample + shadow ray)
         if (!bsdf_is_delta(bsdf) && sv.n_emitters > 0) {
-            float epdf;
-            int ei = pick_emitter(sv, sp, epdf);
-            EmitterSampleRec er = emitter_sample(sv.emitters[ei], sv.emitter_geom(), pos, it.shading_n, sp);
+            const EmitterPick pick = pick_emitter_rec(sv, sp);
+            const auto& nee = pick.e;
+            const float epdf = pick.pdf;
+            EmitterSampleRec er = emitter_sample(nee, sv.emitter_geom(), pos, it.shading_n, sp);
             if (er.pdf > 0.f && !er.radiance.is_zero()) {
                 Vec3 to_l = er.pos - pos;
                 float dist = to_l.length();
@@ -147,11 +151,15 @@ HD bool path_shade_hit(const SceneView& sv, PathState& ps, Sampler& sp, TravCtx 
                 Vec3 f = bsdf_eval(bsdf, -ray.d, wi, it, sv.textures);
                 if (!f.is_zero()) {
                     Ray sh_ray(fmadd(wi, EPSILON, pos), wi);
-                    float sh_max = (sv.emitters[ei].type == EM_ENVMAP ? ENVMAP_DIST : dist) - 2.f * EPSILON;
+                    float sh_max = (nee.type == EM_ENVMAP ? ENVMAP_DIST : dist) - 2.f * EPSILON;
+                    // The MIS pdf is taken before the walk and the BSDF record
+                    // is gathered whole once more behind it (one round trip):
+                    // holding the 20-VGPR copy across scene_occluded measured
+                    // slower (profiles/README.md).
+                    const float pdf_b = er.delta ? 0.f : bsdf_pdf(bsdf, -ray.d, wi, it, sv.textures);
                     if (!scene_occluded(sv, sh_ray, sh_max, tc)) {
                         float light_pdf = er.pdf * epdf;
-                        float w = er.delta ? 1.f
-                                           : mis_weight(light_pdf, bsdf_pdf(bsdf, -ray.d, wi, it, sv.textures));
+                        float w = er.delta ? 1.f : mis_weight(light_pdf, pdf_b);
                         if (tof_in_range(sv.md, path_time + dist))
                             L += thp * f * er.radiance * (w / light_pdf);
                     }
@@ -160,7 +168,8 @@ HD bool path_shade_hit(const SceneView& sv, PathState& ps, Sampler& sp, TravCtx 
         }
 
         // ---- BSDF sampling
-        BsdfSample bs = bsdf_sample(bsdf, -ray.d, it, sp, sv.textures, &ps.lambda);
+        BsdfSample bs = bsdf_sample(load_bsdf(sv.bsdfs, bsdf_id), -ray.d, it, sp, sv.textures,
+                                    &ps.lambda);
         if (bs.pdf <= 0.f || bs.weight.is_zero()) return true;
         if (bs.weight.has_nan() || bs.wi.has_nan()) return true;  // numeric scrub
         thp *= bs.weight;

@@ -22,9 +22,9 @@ template <typename SPLAT_FN>
 HD void trace_light_path_impl(const SceneView& sv, Sampler& sp, SPLAT_FN&& splat, TravCtx tc,
                               int spec_constraint, float caustic_scaling) {
     if (sv.n_emitters <= 0) return;
-    float epdf;
-    int ei = pick_emitter(sv, sp, epdf);
-    const EmitterParams& em = sv.emitters[ei];
+    const EmitterPick pick = pick_emitter_rec(sv, sp);
+    const auto& em = pick.e;
+    const float epdf = pick.pdf;
     EmitterLeRec le = emitter_sample_le(em, sv.emitter_geom(), sp);
     if (!le.valid) return;
 
@@ -73,12 +73,12 @@ HD void trace_light_path_impl(const SceneView& sv, Sampler& sp, SPLAT_FN&& splat
         HitRecord hit = scene_intersect(sv, ray, MAX_DIST, tc);
         if (hit.prim_idx < 0) break;
         Vec3 pos = ray.at(hit.t);
-        uint32_t po = sv.prim_obj[hit.prim_idx];
-        bool is_sphere = (po & PRIM_SPHERE_BIT) != 0;
-        const ObjInfo& obj = sv.objs[po & PRIM_OBJ_MASK];
+        const HitShade hs = load_hit_shade(sv, hit.prim_idx);
+        const bool is_sphere = shade_is_sphere(hs.word);
+        const int bsdf_id = shade_bsdf_id(hs.word);
+        const auto& bsdf = load_bsdf(sv.bsdfs, bsdf_id);
         const Prim prim = sv.prims[hit.prim_idx];
-        Interaction it = get_interaction(prim, sv.attrs[hit.prim_idx], is_sphere, pos, hit.u, hit.v);
-        const BsdfParams& bsdf = sv.bsdfs[obj.bsdf_id];
+        Interaction it = get_interaction(prim, hs.attr, is_sphere, pos, hit.u, hit.v);
 
         // connect this vertex to the camera through the (adjoint) BSDF
         if (!bsdf_is_delta(bsdf)) {
@@ -87,7 +87,9 @@ HD void trace_light_path_impl(const SceneView& sv, Sampler& sp, SPLAT_FN&& splat
             connect(pos, thp * f, n_spec);
         }
 
-        BsdfSample bs = bsdf_sample(bsdf, -ray.d, it, sp, sv.textures, &path_lambda);
+        // gathered once more behind connect()'s shadow walk (integrator.h)
+        BsdfSample bs = bsdf_sample(load_bsdf(sv.bsdfs, bsdf_id), -ray.d, it, sp, sv.textures,
+                                    &path_lambda);
         if (bs.pdf <= 0.f || bs.weight.is_zero() || bs.weight.has_nan() || bs.wi.has_nan()) break;
         thp *= bs.weight;
         if (bs.lobe & (LOBE_SPECULAR | LOBE_TRANSMIT)) ++n_spec;

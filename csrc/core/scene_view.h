@@ -14,6 +14,7 @@
 #include "emitter.h"
 #include "camera.h"
 #include "medium.h"
+#include "shade_load.h"
 
 namespace hippt {
 
@@ -51,11 +52,15 @@ struct SceneView {
     const BVH8Node* nodes8; int n_nodes8;   // A/B: used when non-null
     const Prim* prims; const PrimAttr* attrs; const uint32_t* prim_obj; int n_prims;
     const ObjInfo* objs; int n_objs;
+    // per-primitive shade word (shade_load.h): sphere bit, emitter, bsdf id
+    const uint32_t* prim_shade;
     // materials / emitters / textures
     const BsdfParams* bsdfs; int n_bsdfs;
     const EmitterParams* emitters; int n_emitters;
     const int* emitter_prims;
     const float* emitter_cdf;
+    // one 128-byte record per entry of emitter_prims (emitter.h LightPrim)
+    const LightPrim* light_prims;
     // envmap luminance-CDF tables (importance-sampled NEE; null = cosine)
     const float* env_rows; const float* env_cols; int env_w, env_h;
     // power-proportional light selection CDF (null = uniform, reference)
@@ -86,7 +91,7 @@ struct SceneView {
     int cache_nodes;
 
     HD EmitterGeom emitter_geom() const {
-        return {prims, attrs, prim_obj, emitter_prims, emitter_cdf, textures,
+        return {light_prims, emitter_cdf, textures,
                 env_rows, env_cols, env_w, env_h,
                 scene_bound.xyz(), scene_bound.w};
     }
@@ -114,6 +119,32 @@ HD int pick_emitter(const SceneView& sv, Sampler& sp, float& pdf) {
     i = i >= sv.n_emitters ? sv.n_emitters - 1 : i;
     pdf = 1.f / sv.n_emitters;
     return i;
+}
+
+// pick_emitter with the picked record: the two selection-CDF words of the
+// pdf and the EmitterParams gather are issued together, behind one wait
+// (shade_load.h).  Same sampler draws, same pdf expression as pick_emitter +
+// emitter_sel_pdf.  Requires sv.n_emitters > 0.
+// (Reference member on the host, value on the device: a function-local
+// temporary only, never stored or passed to a kernel; see HitShade.)
+struct EmitterPick {
+#if HIPPT_ON_DEVICE
+    EmitterParams e;
+#else
+    const EmitterParams& e;
+#endif
+    int i;
+    float pdf;
+};
+HD EmitterPick pick_emitter_rec(const SceneView& sv, Sampler& sp) {
+    float pdf;
+    if (sv.emitter_sel_cdf) {
+        const int i = cdf_find(sv.emitter_sel_cdf, sv.n_emitters, sp.next1f());
+        const auto& e = load_emitter_sel(sv.emitters, sv.emitter_sel_cdf, i, pdf);
+        return {e, i, pdf};
+    }
+    const int i = pick_emitter(sv, sp, pdf);
+    return {load_emitter(sv.emitters, i), i, pdf};
 }
 
 // Traversal entry points used by every integrator/kernel.  The 4-wide

@@ -53,6 +53,10 @@ int wf_sort_probe(const uint32_t* status, int n, const uint32_t* gather, int m,
 int wf_trace_probe(const SceneView& sv, const float* ray_o_tmax, const float* ray_d,
                    int n, int lds_n, int n_cached, float* hit_out, int* occ_out,
                    int* plan_out);
+// shade_probe runs shade_probe_record (core/shade_load.h) for n primitive
+// indices, each already checked against sv.n_prims by the caller; out: n x
+// SHADE_PROBE_WORDS dwords.
+int shade_probe(const SceneView& sv, const int* prim_idx, int n, uint32_t* out);
 
 // device helpers used by bind.cpp
 int dev_malloc(void** p, size_t n);

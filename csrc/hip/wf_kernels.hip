@@ -105,8 +105,7 @@ void k_wf_raygen(SceneView sv, WfState st, int spp_idx, uint32_t seed, int lds_n
             st.L[i] = make_float4(le.x, le.y, le.z, 0.f);
         }
     } else {
-        uint32_t oi = sv.prim_obj[hit.prim_idx] & PRIM_OBJ_MASK;
-        status = (uint32_t)(sv.objs[oi].bsdf_id & 0x3F);
+        status = (uint32_t)(shade_bsdf_id(sv.prim_shade[hit.prim_idx]) & 0x3F);
     }
     st.status[i] = (status << 24) | (uint32_t)i;
 }
@@ -240,24 +239,23 @@ void k_wf_shade(SceneView sv, WfState st, const uint32_t* __restrict__ order,
     Sampler sp(st.rng[i]);
 
     Vec3 pos = ray.at(h4.x);
-    uint32_t po = sv.prim_obj[prim_idx];
-    bool is_sphere = (po & PRIM_SPHERE_BIT) != 0;
-    const ObjInfo& obj = sv.objs[po & PRIM_OBJ_MASK];
-    const Prim prim = sv.prims[prim_idx];
-    Interaction it = get_interaction(prim, sv.attrs[prim_idx], is_sphere, pos, h4.y, h4.z);
-    const BsdfParams& bsdf = sv.bsdfs[obj.bsdf_id];
+    const HitShade hs = load_hit_shade(sv, prim_idx);
+    const bool is_sphere = shade_is_sphere(hs.word);
+    const int emitter_id = shade_emitter_id(hs.word);
+    const auto& bsdf = load_bsdf(sv.bsdfs, shade_bsdf_id(hs.word));
+    Interaction it = get_interaction(sv.prims[prim_idx], hs.attr, is_sphere, pos, h4.y, h4.z);
     if (bsdf.tex[TEX_NORMAL] >= 0)
         it.shading_n = apply_normal_map(sv.textures, bsdf.tex[TEX_NORMAL], it.uv, it.shading_n);
 
     // emitter-hit MIS accumulation
-    if (obj.emitter_id >= 0) {
-        const EmitterParams& em = sv.emitters[obj.emitter_id];
+    if (emitter_id >= 0) {
+        const auto& em = load_emitter(sv.emitters, emitter_id);
         Vec3 le = emitter_eval_le(em, it.shading_n, -ray.d, it.uv, sv.textures);
         if (!le.is_zero()) {
             float w = 1.f;
             if (!prev_delta) {
                 float light_pdf = emitter_pdf_hit(em, ray.d, h4.x, it.shading_n, prev_n, sv.emitter_geom()) *
-                                emitter_sel_pdf(sv, obj.emitter_id);
+                                emitter_sel_pdf(sv, emitter_id);
                 w = mis_weight(prev_pdf, light_pdf);
             }
             L += thp * le * w;
@@ -266,17 +264,17 @@ void k_wf_shade(SceneView sv, WfState st, const uint32_t* __restrict__ order,
 
     // NEE: enqueue the shadow ray; visibility resolved by k_wf_shadow
     if (!bsdf_is_delta(bsdf) && sv.n_emitters > 0) {
-        float epdf;
-        int ei = pick_emitter(sv, sp, epdf);
-        EmitterSampleRec er = emitter_sample(sv.emitters[ei], sv.emitter_geom(), pos,
-                                             it.shading_n, sp);
+        const EmitterPick pick = pick_emitter_rec(sv, sp);
+        const auto& nee = pick.e;
+        const float epdf = pick.pdf;
+        EmitterSampleRec er = emitter_sample(nee, sv.emitter_geom(), pos, it.shading_n, sp);
         if (er.pdf > 0.f && !er.radiance.is_zero()) {
             Vec3 to_l = er.pos - pos;
             float dist = to_l.length();
             Vec3 wi = to_l * (1.f / fmaxf(dist, 1e-9f));
             Vec3 f = bsdf_eval(bsdf, -ray.d, wi, it, sv.textures);
             if (!f.is_zero()) {
-                float sh_max = (sv.emitters[ei].type == EM_ENVMAP ? ENVMAP_DIST : dist) - 2.f * EPSILON;
+                float sh_max = (nee.type == EM_ENVMAP ? ENVMAP_DIST : dist) - 2.f * EPSILON;
                 float light_pdf = er.pdf * epdf;
                 float w = er.delta ? 1.f
                                    : mis_weight(light_pdf, bsdf_pdf(bsdf, -ray.d, wi, it, sv.textures));
@@ -389,8 +387,7 @@ __device__ inline void wf_trace_finish(const SceneView& sv, WfState& st, int i,
             st.L[i] = make_float4(L.x, L.y, L.z, l4.w);
         }
     } else {
-        uint32_t oi = sv.prim_obj[hit.prim_idx] & PRIM_OBJ_MASK;
-        status = (uint32_t)(sv.objs[oi].bsdf_id & 0x3F);
+        status = (uint32_t)(shade_bsdf_id(sv.prim_shade[hit.prim_idx]) & 0x3F);
     }
     st.status[i] = (status << 24) | (uint32_t)i;
 }
@@ -527,8 +524,7 @@ __device__ __forceinline__ void wf_step_core(const SceneView& sv, WfState& st, i
             nh.t = MAX_DIST;
             path_shade_hit(sv, ps, sp, tc, nh);  // miss branch: envmap + MIS
         } else {
-            uint32_t oi = sv.prim_obj[nh.prim_idx] & PRIM_OBJ_MASK;
-            status = (uint32_t)(sv.objs[oi].bsdf_id & 0x3F);
+            status = (uint32_t)(shade_bsdf_id(sv.prim_shade[nh.prim_idx]) & 0x3F);
         }
         st.hit[i] = make_float4(nh.t, nh.u, nh.v, int_as_float(nh.prim_idx));
     }
@@ -899,6 +895,37 @@ int wf_trace_probe(const SceneView& sv, const float* ray_o_tmax, const float* ra
     if (e) return e;
     e |= (int)hipMemcpy(hit_out, d_hit.p, (size_t)n * 16, hipMemcpyDeviceToHost);
     e |= (int)hipMemcpy(occ_out, d_occ.p, (size_t)n * 4, hipMemcpyDeviceToHost);
+    return e;
+}
+
+// The records a hit gathers, through the loaders the shaders use.
+__global__ __launch_bounds__(256)
+void k_shade_probe(SceneView sv, const int* __restrict__ prim_idx, int n,
+                   uint32_t* __restrict__ out) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int pid = prim_idx[i];
+    if (pid < 0 || pid >= sv.n_prims) return;   // row stays zero
+    shade_probe_record(sv, pid, out + (size_t)i * SHADE_PROBE_WORDS);
+}
+
+int shade_probe(const SceneView& sv, const int* prim_idx, int n, uint32_t* out) {
+    if (n <= 0 || sv.n_prims <= 0) return (int)hipErrorInvalidValue;
+    DevBuf<int> d_idx;
+    DevBuf<uint32_t> d_out;
+    int e = 0;
+    e |= d_idx.alloc(n);
+    e |= d_out.alloc((size_t)n * SHADE_PROBE_WORDS);
+    if (e) return e;
+    e |= (int)hipMemcpy(d_idx.p, prim_idx, (size_t)n * 4, hipMemcpyHostToDevice);
+    e |= (int)hipMemset(d_out.p, 0, (size_t)n * SHADE_PROBE_WORDS * 4);
+    if (e) return e;
+    hipLaunchKernelGGL(k_shade_probe, dim3((n + 255) / 256), dim3(256), 0, nullptr,
+                       sv, d_idx.p, n, d_out.p);
+    e |= (int)hipGetLastError();
+    e |= (int)hipDeviceSynchronize();
+    if (e) return e;
+    e |= (int)hipMemcpy(out, d_out.p, (size_t)n * SHADE_PROBE_WORDS * 4, hipMemcpyDeviceToHost);
     return e;
 }
 

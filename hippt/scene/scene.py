@@ -389,6 +389,10 @@ class Scene:
                                     prim_base, prim_cnt, inv_area)
         self.native.set_emitter_prims(np.asarray(eprims, np.int32),
                                       np.asarray(ecdf, np.float32))
+        # test hooks: what set_emitter_prims was given (tests/shade_util.py
+        # recomputes the NEE light records from them)
+        self._np["emitter_prims"] = np.asarray(eprims, np.int32)
+        self._np["emitter_cdf"] = np.asarray(ecdf, np.float32)
 
         # power-proportional light selection (extension; HIPPT_LIGHT_POWER=0
         # restores the reference's uniform pick).  Any positive weights are
@@ -503,6 +507,17 @@ class Scene:
                                                           lds_n, n_cached)
         self.last_trace_plan = tuple(plan)   # (lds_n, n_cached) actually used
         return t, prim, u, v, occ.astype(bool)
+
+    def shade_probe(self, prim_idx, device: int = -1):
+        """The raw records a hit on each primitive of prim_idx (BVH order)
+        gathers, through the loaders the shaders use: (attr (n,16), word (n,),
+        bsdf (n,20), emitter (n,16)) as uint32; the emitter words are zero
+        for a primitive that is not an emitter.  device=-1 runs on the host,
+        device>=0 on that GPU."""
+        prim_idx = np.ascontiguousarray(prim_idx, np.int32).reshape(-1)
+        if device >= 0 and self._uploaded_device != device:
+            self.upload(device)
+        return tuple(np.asarray(a) for a in self.native.shade_probe(prim_idx, device))
 
     def update_camera(self, pos=None, lookat=None, up=None, fov=None):
         c = self.desc.camera
