@@ -9,8 +9,10 @@
 #include <pybind11/numpy.h>
 #include <pybind11/stl.h>
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <stdexcept>
+#include <string>
 
 #include "core/scene_view.h"
 #include "core/integrator.h"
@@ -105,6 +107,17 @@ std::vector<uint32_t> make_prim_shade(const uint32_t* prim_obj, size_t n_prims,
     return out;
 }
 
+// Node order of the traversal mirrors: "area" | "level" | "dfs"; null or
+// empty = the default (the winner of the measured ladder, profiles/README.md).
+static BVH4TopOrder top_order_from(const char* name) {
+    if (!name || !*name) return BVH4_TOP_ORDER_DEFAULT;
+    const std::string s(name);
+    if (s == "area") return TOP_AREA;
+    if (s == "level") return TOP_LEVEL;
+    if (s == "dfs") return TOP_DFS;
+    throw std::runtime_error("top order must be area, level or dfs, not '" + s + "'");
+}
+
 struct SceneHolder {
     // ----- host data (kept alive / owned)
     farr np_prims, np_attrs, np_nodes, np_nodes4, np_nodes8;
@@ -176,12 +189,20 @@ struct SceneHolder {
         bvh4_depth = np_nodes4.ndim() == 2 && np_nodes4.shape(0) > 0
             ? bvh4_tree_depth((const BVH4Node*)np_nodes4.data(), (int)np_nodes4.shape(0))
             : 0;
-        nodes4q = np_nodes4.ndim() == 2 && np_nodes4.shape(0) > 0
-            ? quantize_bvh4((const BVH4Node*)np_nodes4.data(), (int)np_nodes4.shape(0))
-            : std::vector<BVH4NodeQ>();
-        nodes4t = np_nodes4.ndim() == 2 && np_nodes4.shape(0) > 0
-            ? tag_bvh4((const BVH4Node*)np_nodes4.data(), (int)np_nodes4.shape(0))
-            : std::vector<BVH4NodeT>();
+        // The traversal mirrors are built from a top-first copy of the tree
+        // (bvh4_top_first, bvh4.h): the LDS node cache holds their first
+        // nodes.  np_nodes4 and everything that works on it keep the
+        // builder's depth-first order.  HIPPT_TOP_ORDER is read per scene.
+        nodes4q.clear();
+        nodes4t.clear();
+        if (np_nodes4.ndim() == 2 && np_nodes4.shape(0) > 0) {
+            std::vector<int32_t> perm;
+            const std::vector<BVH4Node> top = bvh4_top_first(
+                (const BVH4Node*)np_nodes4.data(), (int)np_nodes4.shape(0), BVH4_TOP_ORDERED,
+                top_order_from(getenv("HIPPT_TOP_ORDER")), perm);
+            nodes4q = quantize_bvh4(top.data(), (int)top.size());
+            nodes4t = tag_bvh4(top.data(), (int)top.size());
+        }
         // scene bounding sphere (envmap sample_le disk origin)
         const Prim* pr = (const Prim*)np_prims.data();
         const uint32_t* po = np_prim_obj.data();
@@ -1072,6 +1093,21 @@ uarr py_bvh4_tag(farr nodes4) {
     return out;
 }
 
+// bvh4_top_first on a (m,32) BVH4 array: (reordered nodes4, perm) with
+// perm[source index] = new index.
+py::tuple py_bvh4_top_first(farr nodes4, int n_top, const std::string& order) {
+    if (nodes4.ndim() != 2 || nodes4.shape(1) != 32) throw std::runtime_error("nodes4 must be (m,32)");
+    std::vector<int32_t> perm;
+    const std::vector<BVH4Node> top = bvh4_top_first(
+        (const BVH4Node*)nodes4.data(), (int)nodes4.shape(0), n_top,
+        top_order_from(order.c_str()), perm);
+    farr out({(py::ssize_t)top.size(), (py::ssize_t)32});
+    std::memcpy(out.mutable_data(), top.data(), top.size() * sizeof(BVH4Node));
+    iarr p((py::ssize_t)perm.size());
+    std::memcpy(p.mutable_data(), perm.data(), perm.size() * sizeof(int32_t));
+    return py::make_tuple(out, p);
+}
+
 // Node-visit self-test: for every (ray, node) pair one ordered visit the
 // BVH4Node way (run-time key count, network in nested ifs, push loop,
 // per-child tagging) and one the tagged-node way (BVH_VISIT_TAGGED4), each on
@@ -1315,6 +1351,8 @@ PYBIND11_MODULE(_C, m) {
     m.def("collapse_bvh8", &py_collapse_bvh8, py::arg("nodes"));
     m.def("bvh4_hit", &py_bvh4_hit);
     m.def("bvh4_tag", &py_bvh4_tag, py::arg("nodes4"));
+    m.def("bvh4_top_first", &py_bvh4_top_first, py::arg("nodes4"),
+          py::arg("n_top") = BVH4_TOP_ORDERED, py::arg("order") = "");
     m.def("bvh4_visit_selftest", &py_bvh4_visit_selftest, py::arg("nodes4"),
           py::arg("ray_o"), py::arg("ray_d"), py::arg("tmax"));
     m.def("bvh4_any_visit_selftest", &py_bvh4_any_visit_selftest, py::arg("nodes4"),
@@ -1399,4 +1437,6 @@ PYBIND11_MODULE(_C, m) {
     m.attr("R_BVH_COST") = (int)R_BVH_COST;
     m.attr("R_MEGAKERNEL_PT_DYN") = (int)R_MEGAKERNEL_PT_DYN;
     m.attr("WAVE_SIZE") = 64;
+    m.attr("BVH4_TOP_ORDERED") = BVH4_TOP_ORDERED;
+    m.attr("TRAV_CACHE_STRIDE") = bvh_cache_stride<TravNode>();  // launchers' node_bytes
 }

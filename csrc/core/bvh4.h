@@ -53,7 +53,9 @@
 // (device code only when built with HIPPT_QBVH=1), and the 8-wide walks of
 // bvh8.h.
 #pragma once
+#include <queue>
 #include <stdexcept>
+#include <vector>
 #include "bvh.h"
 
 namespace hippt {
@@ -556,6 +558,51 @@ HD void bvh4_leaf_hit(const Prim* prims, const uint32_t* prim_obj,
         if (t_ > EPSILON && t_ < (tmax)) return true;                         \
     }
 
+// ------------------------------------------------------- LDS node cache
+// Device kernels copy the first n_cached nodes of the traversal array into
+// LDS (trav_lds.h); a walk reads node `cur` from that copy when cur <
+// n_cached.  Which nodes those are is decided on the host: bvh4_top_first at
+// the end of this file puts the nodes most rays visit first.
+//
+// Cached node i lives at byte i * TRAV_CACHE_STRIDE of the copy.  At the
+// node's own 128 bytes, field f of node i falls on LDS banks 32*i + f/4 ..
+// +3 (mod 64): all even nodes share one set of four banks and all odd nodes
+// the other, so sixteen lanes on sixteen cached nodes are an 8-way conflict
+// on each of the visit's 16-byte reads.  At 144 bytes node i starts on bank
+// 36*i mod 64, and sixteen consecutive nodes cover the 64 banks once.
+// Measured, the packed layout wins all the same: the padded one costs a
+// select and a shift-add per visit and a stack entry of LDS per block, and
+// the kitchen comes out 0.6-1.9 Msamples/s slower at every order and cache
+// size (profiles/README.md).  HIPPT_CACHE_STRIDE=144 (setup.py) builds the
+// padded layout for A/B runs.
+#ifndef HIPPT_CACHE_STRIDE
+#define HIPPT_CACHE_STRIDE 128
+#endif
+constexpr int TRAV_CACHE_STRIDE = HIPPT_CACHE_STRIDE;   // of the 128-byte node
+static_assert(TRAV_CACHE_STRIDE >= 128 && TRAV_CACHE_STRIDE % 16 == 0,
+              "cached nodes are read with 16-byte loads");
+// The same padding behind a node of another size (the quantized node).
+template <class Node>
+constexpr int bvh_cache_stride() { return (int)sizeof(Node) + (TRAV_CACHE_STRIDE - 128); }
+// Address of node cur: one address, one load sequence behind it.  The two
+// strides differ by the padding only, so the offset is built in 16-byte
+// units, cur * sizeof/16 plus cur * pad/16 when cached: a select and a
+// shift-add more than the packed layout, no multiply and no second path.
+// (A node index is below 2^27, so the units fit 32 bits.)
+template <class Node>
+HD const Node* bvh_node_at(const Node* nodes, const Node* top_cache, int n_cached,
+                           uint32_t cur) {
+    constexpr uint32_t PAD16 = (uint32_t)(bvh_cache_stride<Node>() - (int)sizeof(Node)) / 16u;
+    const bool cached = (int)cur < n_cached;
+    const Node* nsrc = cached ? top_cache : nodes;
+    if constexpr (PAD16 == 0) {
+        return nsrc + cur;
+    } else {
+        const uint32_t units = cur * (uint32_t)(sizeof(Node) / 16) + (cached ? cur * PAD16 : 0u);
+        return (const Node*)((const char*)nsrc + (size_t)units * 16);
+    }
+}
+
 // ------------------------------------------------------ while-while walks
 // Aila & Laine style phase batching, re-derived for wave64: lanes alternate
 // between a node-walk phase and a leaf-test phase at the OUTER loop level,
@@ -579,11 +626,10 @@ HD HitRecord bvh_closest_ww(const Node* nodes, const Prim* prims,
     for (;;) {
         // ---- node phase: walk internal nodes until a leaf surfaces
         while (bvh4_is_node(cur)) {
-            // top-of-tree nodes come from the LDS copy (every walk starts at
-            // the root; 95% L2 hit rate means the bound is hit LATENCY, and
-            // LDS is ~4x closer than L2).  Pointer select, single flat load.
-            const Node* nsrc = (int)cur < n_cached ? top_cache : nodes;
-            const Node nd = nsrc[cur];
+            // the first n_cached nodes come from the LDS copy (top-first
+            // order: the nodes most walks visit; LDS is ~4x closer than L2).
+            // Address select, single flat load.
+            const Node nd = *bvh_node_at(nodes, top_cache, n_cached, cur);
             uint32_t next;
             BVH_VISIT(Node, next, nd, inv_d, o_div, rec.t, stack, sp, lds_slot, lds_n)
             if (next != BVH4_NONE_W) { cur = next; continue; }
@@ -616,8 +662,7 @@ HD bool bvh_any_ww(const Node* nodes, const Prim* prims, const uint32_t* prim_ob
     uint32_t cur = 0;
     for (;;) {
         while (bvh4_is_node(cur)) {
-            const Node* nsrc = (int)cur < n_cached ? top_cache : nodes;
-            const Node nd = nsrc[cur];
+            const Node nd = *bvh_node_at(nodes, top_cache, n_cached, cur);
             uint32_t next = BVH4_NONE_W;
             if constexpr (BVH4_ANY_STRAIGHT && Node::WIDTH == 4 && Node::TAGGED) {
                 BVH_VISIT_ANY4(next, nd, inv_d, o_div, tmax, stack, sp, lds_slot, lds_n)
@@ -853,6 +898,89 @@ inline std::vector<BVH4NodeT> tag_bvh4(const BVH4Node* nodes, int n) {
             t.child[c] = bvh4_child_word(s.child[c], s.cnt[c]);
             t.pad[c] = 0;
         }
+    }
+    return out;
+}
+
+// Host-side node order for the traversal mirrors: the nodes most walks visit
+// first, so that the LDS node cache (the first n_cached nodes, whatever
+// n_cached a launch is granted) holds the tree's top.  collapse_bvh4 numbers
+// nodes depth-first: its first 64 are the root, one node per level down the
+// leftmost spine and one corner of the scene.
+//   * The root stays node 0.
+//   * Positions 1 .. min(n, n_top)-1 are filled one at a time from the open
+//     set, the not yet placed internal children of the nodes placed so far,
+//     with the open node of the highest priority; ties go to the lower source
+//     index.  So every prefix is closed under "parent", and one order serves
+//     every cache size.
+//       TOP_AREA   priority = surface area of the node's box in its parent's
+//                  slot, computed in double (a ray's chance to reach it)
+//       TOP_LEVEL  priority = -depth (breadth first)
+//       TOP_DFS    the input order, untouched
+//   * All other nodes follow in their source order: deep subtrees stay
+//     contiguous.
+// Internal child indices are renumbered; boxes, leaf words, counts and the
+// slot order are copied untouched, so a walk visits the same boxes and prims
+// in the same order and only the node indices it carries differ.
+// perm[source index] = new index.
+constexpr int BVH4_TOP_ORDERED = 512;   // above the largest cache lds_plan grants
+enum BVH4TopOrder { TOP_DFS = 0, TOP_LEVEL = 1, TOP_AREA = 2 };
+constexpr BVH4TopOrder BVH4_TOP_ORDER_DEFAULT = TOP_AREA;   // HIPPT_TOP_ORDER overrides
+inline std::vector<BVH4Node> bvh4_top_first(const BVH4Node* nodes, int n, int n_top,
+                                            BVH4TopOrder order, std::vector<int32_t>& perm) {
+    if (n < 0) n = 0;
+    perm.resize((size_t)n);
+    for (int i = 0; i < n; ++i) perm[i] = i;
+    std::vector<BVH4Node> out(nodes, nodes + n);
+    const int k_top = n_top < n ? n_top : n;
+    if (order == TOP_DFS || k_top <= 1) return out;
+    for (int i = 0; i < n; ++i)
+        for (int c = 0; c < 4; ++c)
+            if (nodes[i].child[c] >= n)
+                throw std::runtime_error("bvh4_top_first: child index beyond the node array");
+    struct Open { double prio; int node; };
+    struct Later {   // a comes out of the queue after b
+        bool operator()(const Open& a, const Open& b) const {
+            return a.prio < b.prio || (a.prio == b.prio && a.node > b.node);
+        }
+    };
+    std::priority_queue<Open, std::vector<Open>, Later> open;
+    std::vector<int> depth((size_t)n, 0);
+    std::vector<char> placed((size_t)n, 0);
+    std::vector<int> src;   // src[new index] = source index
+    src.reserve((size_t)n);
+    auto place = [&](int i) {
+        placed[i] = 1;
+        src.push_back(i);
+        const BVH4Node& s = nodes[i];
+        for (int c = 0; c < 4; ++c) {
+            const int ch = s.child[c];
+            if (ch < 0 || placed[ch]) continue;
+            depth[ch] = depth[i] + 1;
+            double prio = -(double)depth[ch];
+            if (order == TOP_AREA) {
+                const double dx = (double)s.hi_x[c] - (double)s.lo_x[c];
+                const double dy = (double)s.hi_y[c] - (double)s.lo_y[c];
+                const double dz = (double)s.hi_z[c] - (double)s.lo_z[c];
+                prio = 2.0 * (dx * dy + dy * dz + dz * dx);
+                if (!(prio >= 0.0)) prio = 0.0;   // inverted or NaN box
+            }
+            open.push({prio, ch});
+        }
+    };
+    place(0);
+    while ((int)src.size() < k_top && !open.empty()) {
+        const int i = open.top().node;
+        open.pop();
+        if (!placed[i]) place(i);
+    }
+    for (int i = 0; i < n; ++i)
+        if (!placed[i]) src.push_back(i);
+    for (int k = 0; k < n; ++k) perm[src[k]] = k;
+    for (int k = 0; k < n; ++k) {
+        out[k] = nodes[src[k]];
+        for (int c = 0; c < 4; ++c)
+            if (out[k].child[c] >= 0) out[k].child[c] = perm[out[k].child[c]];
     }
     return out;
 }

@@ -209,7 +209,7 @@ int launch_render(const SceneView& sv, float* accum, float* var,
                     : is_rest ? OCC_REST : OCC_PT;
     static const bool stack_in_lds = !env_is("HIPPT_STACK", "scratch");
     const LdsPlan plan = lds_plan(occ_v, stack_in_lds, false, sv.n_nodes4,
-                                  (int)sizeof(TravNode), top_cache_request(sv));
+                                  TRAV_CACHE_NODE_BYTES, top_cache_request(sv));
     const int lds_n = plan.lds_n, n_cached = plan.n_cached;
     const uint32_t shmem = plan.shmem;
     const int w = sv.cam.w, h = sv.cam.h;

@@ -694,7 +694,7 @@ static int wf_occ() {
 // pass through the same clamps.
 static LdsPlan wf_lds_plan(const SceneView& sv, int lds_req = -1, int cache_in = -1) {
     static const bool stack_in_lds = !env_is("HIPPT_WF_STACK", "scratch");
-    return lds_plan(wf_occ(), stack_in_lds, true, sv.n_nodes4, (int)sizeof(TravNode),
+    return lds_plan(wf_occ(), stack_in_lds, true, sv.n_nodes4, TRAV_CACHE_NODE_BYTES,
                     top_cache_request(sv, cache_in), lds_req);
 }
 

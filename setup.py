@@ -42,6 +42,9 @@ def compile_flags():
     if os.environ.get("HIPPT_QBVH"):
         # quantized 64-byte BVH4 nodes as the traversal tree (A/B build)
         cflags.append("-DHIPPT_QBVH")
+    if os.environ.get("HIPPT_CACHE_STRIDE"):
+        # byte stride of the LDS node cache (bvh4.h TRAV_CACHE_STRIDE; A/B build)
+        cflags.append("-DHIPPT_CACHE_STRIDE=" + str(int(os.environ["HIPPT_CACHE_STRIDE"])))
     ldflags = []
     if os.environ.get("HIPPT_DEBUG"):
         # debuggable build (reference parity: Debug -G -g device debug,
