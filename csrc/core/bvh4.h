@@ -158,6 +158,9 @@ HD uint32_t bvh4_sel4(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3,
 // tagging all four next to the slab tests and selecting the word
 // (profiles/README.md): the compiler sinks the four taggings behind the
 // sort, where they lengthen the chain more than the second select does.
+// That holds for the BVH4Node visits, which build the word from child and
+// cnt; a tagged node stores its words, and BVH_VISIT_TAGGED4 takes all four
+// through the sort with no select at all.
 // (bvh8.h adds the width-8 overload.)
 HD uint32_t bvh_child_word_at(const BVH4Node& nd, uint32_t slot) {
     int ch = (int)bvh4_sel4((uint32_t)nd.child[0], (uint32_t)nd.child[1],
@@ -356,6 +359,15 @@ HD LdsSlot bvh_host_slot(uint64_t* p) { return (LdsSlot)p; }
 // near in unrolled steps.  Hit keys are distinct (the slot is in the low
 // bits), so any correct sort gives the order of the form above: `next` and
 // every pushed entry are the same (tests/test_visit_host.py compares them).
+//
+// Each key travels through the network with its child's word, so nothing
+// behind the sort has to find the word again from the slot bits (a select
+// tree over the four words and a test for the miss key per push, and once
+// more for `next`): a comparator is one compare on the keys and four selects.
+// A missed child's word is BVH4_NONE_W, so misses need no order among
+// themselves; a hit empty slot or leaf of no prims keeps its real key and has
+// the word BVH4_NONE_W, which a push skips and which, as the nearest child,
+// makes `next` BVH4_NONE_W: the walk pops.
 constexpr uint32_t BVH4_MISS_KEY = 0xffffffffu;
 #define BVH_KEY_MINMAX(a, b)                                              \
     {                                                                     \
@@ -363,40 +375,43 @@ constexpr uint32_t BVH4_MISS_KEY = 0xffffffffu;
         const uint32_t hi_ = (a) < (b) ? (b) : (a);                       \
         (a) = lo_; (b) = hi_;                                             \
     }
-#define BVH_KEY4(key, nd, c, inv_d, o_div, tmax)                          \
-    uint32_t key;                                                         \
+#define BVH_PAIR_MINMAX(ka, wa, kb, wb)                                   \
+    {                                                                     \
+        const bool lt_ = (ka) < (kb);                                     \
+        const uint32_t klo_ = lt_ ? (ka) : (kb), khi_ = lt_ ? (kb) : (ka); \
+        const uint32_t wlo_ = lt_ ? (wa) : (wb), whi_ = lt_ ? (wb) : (wa); \
+        (ka) = klo_; (kb) = khi_; (wa) = wlo_; (wb) = whi_;               \
+    }
+#define BVH_PAIR4(key, word, nd, c, inv_d, o_div, tmax)                   \
+    uint32_t key, word;                                                   \
     {                                                                     \
         float enter_, exit_;                                              \
         bvh_child_slab(nd, c, inv_d, o_div, tmax, enter_, exit_);         \
-        key = !bvh_slot_known_empty(nd, c) && enter_ <= exit_             \
-            ? (float_as_uint(enter_) & ~3u) | (uint32_t)(c) : BVH4_MISS_KEY; \
+        const bool hit_ = !bvh_slot_known_empty(nd, c) && enter_ <= exit_; \
+        key = hit_ ? (float_as_uint(enter_) & ~3u) | (uint32_t)(c) : BVH4_MISS_KEY; \
+        word = hit_ ? bvh_filled_child_word(nd, c) : BVH4_NONE_W;         \
     }
-// Tagged word behind a sorted key: BVH4_NONE_W for a miss (and for a hit
-// leaf of no prims, which the word already says).
-#define BVH_KEY4_WORD(nd, key) \
-    ((key) == BVH4_MISS_KEY ? BVH4_NONE_W : bvh_child_word_at(nd, (key) & 3u))
-#define BVH_PUSH_KEY4(nd, key, stack, sp, lds_slot, lds_n)                \
+#define BVH_PUSH_PAIR4(key, word, stack, sp, lds_slot, lds_n)             \
     {                                                                     \
-        const uint32_t w_ = BVH_KEY4_WORD(nd, key);                       \
-        if (w_ != BVH4_NONE_W) {                                          \
-            uint64_t e_ = ((uint64_t)((key) & ~3u) << 32) | w_;           \
+        if ((word) != BVH4_NONE_W) {                                      \
+            uint64_t e_ = ((uint64_t)((key) & ~3u) << 32) | (word);       \
             BVH_PUSH(stack, sp, lds_slot, lds_n, e_)                      \
         }                                                                 \
     }
 #define BVH_VISIT_TAGGED4(next, nd, inv_d, o_div, tmax, stack, sp, lds_slot, lds_n) \
-    BVH_KEY4(k0_, nd, 0, inv_d, o_div, tmax)                              \
-    BVH_KEY4(k1_, nd, 1, inv_d, o_div, tmax)                              \
-    BVH_KEY4(k2_, nd, 2, inv_d, o_div, tmax)                              \
-    BVH_KEY4(k3_, nd, 3, inv_d, o_div, tmax)                              \
-    BVH_KEY_MINMAX(k0_, k1_)                                              \
-    BVH_KEY_MINMAX(k2_, k3_)                                              \
-    BVH_KEY_MINMAX(k0_, k2_)                                              \
-    BVH_KEY_MINMAX(k1_, k3_)                                              \
-    BVH_KEY_MINMAX(k1_, k2_)                                              \
-    BVH_PUSH_KEY4(nd, k3_, stack, sp, lds_slot, lds_n)                    \
-    BVH_PUSH_KEY4(nd, k2_, stack, sp, lds_slot, lds_n)                    \
-    BVH_PUSH_KEY4(nd, k1_, stack, sp, lds_slot, lds_n)                    \
-    next = BVH_KEY4_WORD(nd, k0_);
+    BVH_PAIR4(k0_, w0_, nd, 0, inv_d, o_div, tmax)                        \
+    BVH_PAIR4(k1_, w1_, nd, 1, inv_d, o_div, tmax)                        \
+    BVH_PAIR4(k2_, w2_, nd, 2, inv_d, o_div, tmax)                        \
+    BVH_PAIR4(k3_, w3_, nd, 3, inv_d, o_div, tmax)                        \
+    BVH_PAIR_MINMAX(k0_, w0_, k1_, w1_)                                   \
+    BVH_PAIR_MINMAX(k2_, w2_, k3_, w3_)                                   \
+    BVH_PAIR_MINMAX(k0_, w0_, k2_, w2_)                                   \
+    BVH_PAIR_MINMAX(k1_, w1_, k3_, w3_)                                   \
+    BVH_PAIR_MINMAX(k1_, w1_, k2_, w2_)                                   \
+    BVH_PUSH_PAIR4(k3_, w3_, stack, sp, lds_slot, lds_n)                  \
+    BVH_PUSH_PAIR4(k2_, w2_, stack, sp, lds_slot, lds_n)                  \
+    BVH_PUSH_PAIR4(k1_, w1_, stack, sp, lds_slot, lds_n)                  \
+    next = w0_;
 // The visit a walk over `Node` runs.
 #define BVH_VISIT(Node, next, nd, inv_d, o_div, tmax, stack, sp, lds_slot, lds_n)      \
     if constexpr (Node::WIDTH == 4 && Node::TAGGED) {                                  \
